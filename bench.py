@@ -10,12 +10,20 @@ that stream: rolling-hash scan -> MinSize boundary selection -> SHA-256 of every
 data path (weak scaling); torch.distributed is used only for the barrier and the max-over-ranks
 timing.
 
-The default N=1 run then times configs[2] (256 x 64 MiB streams on the same GPU: the many-blob
-path, the largest single-GPU config) the same way, after freeing the configs[1] buffers, and
-reports it as the nested "configs2" record of the same JSON line (its own value, ms_per_step,
-stage times, roofline and 16-thread CPU baseline). The headline value stays configs[1].
+A plain run does only what the headline figure needs: it sets up, runs W warmup steps, times K
+steps and prints the JSON line (value, ms_per_step, the stage times the steps' own HIP events
+gave, and the rooflines computed from them). --dump-outputs DIR also writes the last timed
+step's records as .npy files, for comparing two builds output for output.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+--full adds every other leg, after the timed steps: the oracle parity check of the records and
+the CPU baseline on the same device bytes, the host-memory legs (end_to_end, writer_e2e) and,
+on the default N=1 workload, configs[2] (256 x 64 MiB streams on the same GPU: the many-blob
+path, the largest single-GPU config) timed the same way after freeing the configs[1] buffers
+and reported as the nested "configs2" record of the same JSON line (its own value,
+ms_per_step, stage times, roofline and 16-thread CPU baseline). The headline value stays
+configs[1].
+
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   (N>1: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...)
 """
 from __future__ import annotations
@@ -43,22 +51,33 @@ def parse():
     ap.add_argument("--streams", type=int, default=1, help="independent streams per GPU")
     ap.add_argument("--bits", type=int, default=16)
     ap.add_argument("--min-size", type=int, default=1024)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's records (rank 0's) as "
+                         "DIR/<name>.npy (float64 / float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the legs beside the headline figure: "
+                         "oracle parity check, CPU baseline, host-memory legs, nested configs[2]")
     ap.add_argument("--cpu-sample-mib", type=int, default=1024,
-                    help="bytes the CPU oracle baseline splits+hashes: a prefix of stream 0 for "
-                         "one stream, else whole streams (at least one per thread) (0: skip)")
+                    help="--full: bytes the CPU oracle baseline splits+hashes: a prefix of stream "
+                         "0 for one stream, else whole streams (at least one per thread) (0: skip)")
     ap.add_argument("--e2e-mib", type=int, default=1024,
-                    help="bytes of host-memory stream for the PCIe-inclusive streaming rate "
-                         "(bsg_write -> records in host memory; 0: skip)")
+                    help="--full: bytes of host-memory stream for the PCIe-inclusive streaming "
+                         "rate (bsg_write -> records in host memory; 0: skip)")
     ap.add_argument("--no-writer-e2e", dest="writer_e2e", action="store_false",
-                    help="skip the split.Writer -> store/mem leg (same host stream as --e2e-mib)")
+                    help="--full: skip the split.Writer -> store/mem leg (same host stream as "
+                         "--e2e-mib)")
     ap.add_argument("--configs2-steps", type=int, default=None,
-                    help="timed steps of the nested configs[2] record (256 x 64 MiB on the same "
-                         "GPU, N=1 default run only; default: --steps, 0: skip)")
+                    help="--full: timed steps of the nested configs[2] record (256 x 64 MiB on "
+                         "the same GPU, N=1 default run only; default: --steps, 0: skip)")
     ap.add_argument("--check", action="store_true",
-                    help="also verify the records against the oracle on bytes generated on the "
-                         "host (checks the device fill too); the default run already checks them "
+                    help="--full: also verify the records against the oracle on bytes generated "
+                         "on the host (checks the device fill too); --full already checks them "
                          "against the oracle on the device bytes (the CPU baseline's sample)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if a.check and not a.full:
+        ap.error("--check needs --full")
     if a.configs2_steps is None:
         a.configs2_steps = a.steps
     return a
@@ -411,10 +430,15 @@ def workload_name(ns: int, nbytes: int, bits: int, min_size: int) -> str:
 
 
 def device_leg(ns: int, nbytes: int, bits: int, min_size: int, steps: int, warmup: int,
-               world: int, rank: int, local: int, cpu_sample: int, check: bool) -> dict:
+               world: int, rank: int, local: int, cpu_sample: int, check: bool,
+               full: bool = True, dump: str | None = None) -> dict:
     """One device-resident workload: ns streams of nbytes generated in HBM, W warmups, K timed
-    steps (each a full scan -> select -> SHA-256 pass, records left in HBM), then the CPU
-    baseline over a bounded sample of the same bytes. Frees its device memory before returning."""
+    steps (each a full scan -> select -> SHA-256 pass, records left in HBM); dump: rank 0 then
+    writes the last step's records there (dump_outputs); full: then the oracle parity check and
+    the CPU baseline over a bounded sample of the same bytes (cpu_sample MiB). Frees its device
+    memory before returning."""
+    if not full:
+        cpu_sample, check = 0, False
     from bs_amd import bsgpu
     stride = (nbytes + 15) & ~15
     buf = bsgpu.DeviceBuffer(stride * ns, device=local)
@@ -468,8 +492,12 @@ def device_leg(ns: int, nbytes: int, bits: int, min_size: int, steps: int, warmu
     chunks = int(eng.nchunks)
     # the last timed step's records, copied to the host after timing: checked below against
     # the oracle on the same device bytes (the metric's "chunk/ref bit-parity" half)
-    dev_ch = eng.chunks()
-    dev_counts = eng.counts() if ns > 1 else None
+    dev_ch = dev_counts = None
+    if full or (dump and rank == 0):
+        dev_ch = eng.chunks()
+        dev_counts = eng.counts() if (ns > 1 or dump) else None
+    if dump and rank == 0:
+        dump_outputs(dump, dev_ch, dev_counts)
     gen_ok = None
     if check and rank == 0:  # --check: also against bytes generated on the host (checks the fill)
         from bs_amd.synth import splitmix_array
@@ -495,7 +523,7 @@ def device_leg(ns: int, nbytes: int, bits: int, min_size: int, steps: int, warmu
             host_streams = [host_all[offs[i]:offs[i] + nbytes] for i in range(k)]
             sample = f"streams 0..{k - 1} of {ns} ({k} x {nbytes >> 20} MiB)"
     check_streams = []
-    if world > 1 and ns == 1:  # N>1: every rank checks its own stream (no CPU baseline there)
+    if full and world > 1 and ns == 1:  # N>1: every rank checks its own stream (no CPU baseline)
         check_streams = [buf.to_host(0, nbytes)]
     # the engine and its input are done with: free them before the next leg
     eng.close()
@@ -552,6 +580,34 @@ def records_match(dev, dev_counts, ref, ns: int, full: bool) -> bool:
             return False
         d, r = dev[:n], ref
     return all(bool((d[f] == r[f]).all()) for f in ("offset", "len", "level", "stream", "ref"))
+
+
+DUMP_MAX_RECORDS = 350_000  # x 160 bytes per record as written below: 56 MB, under 64 MB in all
+DUMP_SEED = 0xD0B5
+
+
+def dump_outputs(out_dir: str, dev, counts) -> None:
+    """--dump-outputs: what a caller of the timed path receives from its last step, the chunk
+    records (bsg_engine_copy_chunks) and the per-stream counts, one .npy per field: offset, len
+    (float64: exact below 2^53), level, stream (float32), ref (float32, one row of the SHA-256's
+    32 bytes per record), counts and nchunks (float64). More than DUMP_MAX_RECORDS records: a
+    fixed sample of them (seeded by DUMP_SEED, so the same rows for the same record count),
+    whose row numbers go to index.npy."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    n = len(dev)
+    if n > DUMP_MAX_RECORDS:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_MAX_RECORDS, replace=False))
+        dev = dev[idx]
+    else:
+        idx = np.arange(n)
+    arrays = {"offset": dev["offset"].astype(np.float64), "len": dev["len"].astype(np.float64),
+              "level": dev["level"].astype(np.float32), "stream": dev["stream"].astype(np.float32),
+              "ref": dev["ref"].astype(np.float32), "index": idx.astype(np.float64),
+              "counts": np.asarray(counts, dtype=np.float64),
+              "nchunks": np.array([n], dtype=np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def pmc_valu(workload: str):
@@ -638,15 +694,16 @@ def main():
     nbytes = args.stream_mib << 20
     ns = args.streams
     leg = device_leg(ns, nbytes, args.bits, args.min_size, args.steps, args.warmup, world, rank,
-                     local, args.cpu_sample_mib, args.check)
+                     local, args.cpu_sample_mib, args.check, args.full, args.dump_outputs)
     elapsed, stage_avg = leg["elapsed"], leg["stage_avg"]
     total_bytes = world * ns * nbytes * args.steps
     value = total_bytes / elapsed / 2**30
     workload = workload_name(ns, nbytes, args.bits, args.min_size)
-    # configs[2] (the largest single-GPU config, the many-blob path) on the same GPU, timed the
-    # same way, as a nested record; the headline stays configs[1]
+    # --full: configs[2] (the largest single-GPU config, the many-blob path) on the same GPU,
+    # timed the same way, as a nested record; the headline stays configs[1]
     c2 = None
-    if (rank == 0 and world == 1 and workload == CONFIGS1 and args.configs2_steps > 0):
+    host_legs = args.full and rank == 0 and world == 1
+    if host_legs and workload == CONFIGS1 and args.configs2_steps > 0:
         n2, ns2 = 64 << 20, 256
         leg2 = device_leg(ns2, n2, 16, 1024, args.configs2_steps, args.warmup, 1, 0, local,
                           args.cpu_sample_mib, False)
@@ -663,10 +720,9 @@ def main():
               "work_roofline": work_roofline(CONFIGS2, leg2["stage_avg"][2], leg2["diag"]),
               "cpu_baseline": leg2["cpu"], "sha_path": leg2["diag"],
               "chain_roofline": chain_roofline(leg2["diag"])}
-    e2e = end_to_end(args.e2e_mib, args.bits, args.min_size, local) \
-        if (rank == 0 and world == 1) else None
+    e2e = end_to_end(args.e2e_mib, args.bits, args.min_size, local) if host_legs else None
     wr = writer_e2e(args.e2e_mib, args.bits, args.min_size, local) \
-        if (rank == 0 and world == 1 and args.writer_e2e) else None
+        if (host_legs and args.writer_e2e) else None
     if wr is not None:  # Root against the C oracle's split.Writer restatement, after timing
         from oracle import oracle as O  # checker only
         data = wr.pop("data")
@@ -716,6 +772,10 @@ def main():
             # bsg_init first unless BSG_BENCH_INIT=0, Python's cyclic GC off inside timed loops
             "host_settings": {"library_knobs": "defaults", "bsg_init": init,
                               "python_gc_in_timed_loops": "off"},
+            # False: a plain run (cpu_baseline, end_to_end, writer_e2e, configs2 and oracle_check
+            # are null: those legs run under --full)
+            "full": args.full,
+            "dumped_outputs": args.dump_outputs,
         }
         line["oracle_check"] = leg["check"]
         line["oracle_checked"] = leg["checked"]

@@ -2,7 +2,9 @@
 
 Checks the keys and types the round-end driver and the judge read: the metric and unit of
 BASELINE.json, the whole-job value, the roofline object (bound, achieved, peak, unit, frac,
-traffic) and the cpu_baseline object (value, unit, cores, kind, sample).
+traffic) and the cpu_baseline object (value, unit, cores, kind, sample). The legs beside the
+headline figure run under --full; a plain run carries the headline alone and --dump-outputs
+writes the last timed step's records.
 """
 import json
 import os
@@ -16,7 +18,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.mark.gpu
 def test_bench_json_line():
-    cmd = [sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--streams", "2",
+    cmd = [sys.executable, "bench.py", "--full", "--steps", "2", "--warmup", "1", "--streams", "2",
            "--stream-mib", "64", "--cpu-sample-mib", "8", "--e2e-mib", "64"]
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -48,8 +50,9 @@ def test_bench_json_line():
 
 @pytest.mark.gpu
 def test_bench_default_carries_configs2():
-    """The default workload (configs[1]) also carries the nested configs[2] record."""
-    cmd = [sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--configs2-steps", "1",
+    """Under --full the default workload (configs[1]) also carries the nested configs[2] record."""
+    cmd = [sys.executable, "bench.py", "--full", "--steps", "2", "--warmup", "1",
+           "--configs2-steps", "1",
            "--cpu-sample-mib", "64", "--e2e-mib", "0"]
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -65,3 +68,51 @@ def test_bench_default_carries_configs2():
     assert c2["cpu_baseline"]["cores"] >= 1 and c2["cpu_baseline"]["full_writer"]["value"] > 0
     assert set(c2["stage_ms"]) == set(d["stage_ms"])
     assert d["oracle_check"] is True and c2["oracle_check"] is True
+
+
+def _plain_run(extra):
+    cmd = [sys.executable, "bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1",
+           "--streams", "3", "--stream-mib", "8"] + extra
+    r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    return json.loads(lines[0])
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_and_dump_outputs(tmp_path, oracle):
+    """A plain run times its steps and nothing else: the legs beside the headline are null.
+    --dump-outputs writes the last timed step's records as float .npy files, the same from run
+    to run, and they are the oracle's chunks of the same seeded streams."""
+    import numpy as np
+    from bs_amd.synth import splitmix_array
+    import bench
+    a, b = str(tmp_path / "a"), str(tmp_path / "b")
+    d = _plain_run(["--dump-outputs", a])
+    _plain_run(["--dump-outputs", b])
+    assert d["full"] is False and d["steps"] == 2 and d["warmup"] == 1
+    assert d["unit"] == "GiB/s" and d["higher_is_better"] is True and d["dtype"] == "u8"
+    for leg in ("cpu_baseline", "end_to_end", "writer_e2e", "configs2", "oracle_check"):
+        assert d[leg] is None, leg
+    # value and ms_per_step are the same measurement: 3 x 8 MiB per step
+    assert d["ms_per_step"] > 0
+    assert abs(d["value"] - (24 / 1024) / (d["ms_per_step"] * 1e-3)) <= 0.02 * d["value"]
+    names = sorted(os.listdir(a))
+    assert names == sorted(os.listdir(b)) and "ref.npy" in names and "offset.npy" in names
+    got = {n[:-4]: np.load(os.path.join(a, n)) for n in names}
+    assert sum(v.nbytes for v in got.values()) <= 64 * 10**6
+    for n in names:
+        assert got[n[:-4]].dtype in (np.float32, np.float64), n
+        assert np.array_equal(got[n[:-4]], np.load(os.path.join(b, n))), n
+    table = oracle.buzhash32_table(1)
+    k = 0
+    assert len(got["counts"]) == 3 and got["nchunks"][0] == got["counts"].sum() == len(got["ref"])
+    for s in range(3):
+        ref = oracle.split(table, splitmix_array(bench.BASE_SEED + s, 8 << 20))
+        c = int(got["counts"][s])
+        assert c == len(ref)
+        for f in ("offset", "len", "level", "ref"):
+            assert np.array_equal(got[f][k:k + c], ref[f].astype(got[f].dtype)), (s, f)
+        assert (got["stream"][k:k + c] == s).all()
+        k += c
