@@ -2,6 +2,7 @@
 from __future__ import annotations
 
 import os
+import re
 import subprocess
 import sys
 
@@ -9,31 +10,37 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libbsgpu.so")
 SOURCES = ["bsgpu_kernels.hip", "bsgpu_host.cpp", "bs_split.cpp", "bs_filestore.cpp"]
-HEADERS = ["bsgpu_internal.h", "host_pool.h", "bsgpu_launch.h", "buzhash32_table.inc", "sha256_device.h",
-           "sha256_skew_block.inc", "sha256_skew_loop.inc", "sha256_oct_loop.inc",
-           "sha256_lane_asm.inc"]
 ARCH = os.environ.get("BSG_OFFLOAD_ARCH", "gfx950")
+_INCLUDE = re.compile(r'^[ \t]*#[ \t]*include[ \t]*"([^"]+)"', re.M)
+
+
+def _deps() -> list[str]:
+    """SOURCES and every file they reach through #include "...", each relative to the file
+    that names it (so ../../include/bsgpu.h works), as normalised absolute paths."""
+    todo = [os.path.join(CSRC, f) for f in SOURCES]
+    seen = []
+    while todo:
+        path = os.path.normpath(todo.pop())
+        if path in seen:
+            continue
+        seen.append(path)
+        with open(path, encoding="utf-8", errors="replace") as f:
+            names = _INCLUDE.findall(f.read())
+        todo += [os.path.join(os.path.dirname(path), n) for n in names]
+    return sorted(seen)
 
 
 def _stale() -> bool:
     if not os.path.exists(LIB):
         return True
     t = os.path.getmtime(LIB)
-    deps = [os.path.join(CSRC, f) for f in SOURCES + HEADERS]
-    deps.append(os.path.join(os.path.dirname(HERE), "include", "bsgpu.h"))
-    deps.append(os.path.join(os.path.dirname(HERE), "include", "bs_split.hpp"))
-    return any(os.path.getmtime(d) > t for d in deps)
+    return any(os.path.getmtime(d) > t for d in _deps())
 
 
-def build_debug(extra=(), name="libbsgpu_dbg.so") -> str:
-    """Device-printf build (libbsgpu_dbg.so) for chasing hangs; never loaded by default."""
-    out = os.path.join(HERE, name)
+def _hipcc_cmd(out: str, extra_flags=()) -> list[str]:
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    cmd = [hipcc, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-shared",
-           "-Wno-unused-value", "-Wno-unused-result", *extra, "-o", out]
-    cmd += [os.path.join(CSRC, f) for f in SOURCES]
-    subprocess.run(cmd, check=True)
-    return out
+    return [hipcc, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-shared",
+            *extra_flags, "-o", out, *(os.path.join(CSRC, f) for f in SOURCES)]
 
 
 def build_locked(out: str, stale, compile_to) -> bool:
@@ -63,13 +70,10 @@ def build_locked(out: str, stale, compile_to) -> bool:
 def build(force: bool = False, verbose: bool = False) -> str:
     if not force and not _stale():
         return LIB
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
     def compile_to(tmp):
-        cmd = [hipcc, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-shared",
-               "-Wall", "-Wno-unused-function", "-Wno-unused-value", "-Wno-unused-result",
-               "-o", tmp]
-        cmd += [os.path.join(CSRC, f) for f in SOURCES]
+        cmd = _hipcc_cmd(tmp, ["-Wall", "-Wno-unused-function", "-Wno-unused-value",
+                               "-Wno-unused-result"])
         if verbose:
             print(" ".join(cmd), file=sys.stderr)
         subprocess.run(cmd, check=True)

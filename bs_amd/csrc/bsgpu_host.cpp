@@ -232,6 +232,41 @@ void stream_release(int device, hipStream_t s) {
   (void)hipStreamDestroy(s);
 }
 
+// A few idle T (an engine, a hasher: device buffers, pinned staging, a stream) kept for the next
+// one-shot call on their device, which otherwise creates and frees one every time (~1 ms of
+// allocations, profiles/r03_split_hash_batch_*). take() hands out one of `device` or nullptr;
+// give() keeps t unless the pool is full, and then the caller frees it. What is given must be
+// idle: its streams synchronised. The pool is never destroyed: what it holds lives until the
+// process exits, when the HIP runtime its destructors would call may be gone already.
+template <class T> class DevicePool {
+ public:
+  T* take(int device) {
+    std::lock_guard<std::mutex> g(mu_);
+    for (size_t i = 0; i < v_.size(); ++i)
+      if (v_[i]->dev == device) {
+        T* t = v_[i];
+        v_.erase(v_.begin() + (long)i);
+        return t;
+      }
+    return nullptr;
+  }
+  bool give(T* t) {
+    std::lock_guard<std::mutex> g(mu_);
+    if (v_.size() >= kKeep) return false;
+    v_.push_back(t);
+    return true;
+  }
+  static DevicePool& get() {
+    static auto* p = new DevicePool();
+    return *p;
+  }
+
+ private:
+  static constexpr size_t kKeep = 2;
+  std::mutex mu_;
+  std::vector<T*> v_;
+};
+
 // CUs of a device (one attribute query; the device-properties call fills the whole struct and
 // costs milliseconds, which an engine per tile slot paid on every bsg_open)
 int device_cus(int device) {
@@ -358,6 +393,29 @@ int normalize(const bsg_params* in, Params* out, bsg_params* norm) {
   return BSG_OK;
 }
 
+// The sizes of one run, computed once per enqueue (bsg_engine::plan_split / plan_hash) from the
+// run's descriptors and parameters: every buffer reservation and argument block reads them here.
+struct RunPlan {
+  uint32_t ns = 0;         // streams
+  uint64_t strips = 0;     // kStrip-byte strips of all streams
+  uint64_t total_len = 0;  // bytes of all streams
+  uint64_t data_span = 1;  // bytes from d_data to the end of the last stream (k_sha regions)
+  uint64_t cand_cap = 0;   // candidate capacity
+  uint64_t chunk_cap = 0;  // record capacity
+  uint32_t lists = 0;      // k_scan's refine lists
+  uint64_t list_cap = 0;   // entries per list
+  uint64_t jobs = 0;       // k_sha's job bound: chunk_cap + ns
+  bool scan = false;       // scan and selection stages (a split run; a hash run has neither)
+  bool early = false;      // early chains on a second stream
+  bool light = false;      // ... in the lightly loaded arrangement (bsg_engine, "Round 5")
+};
+
+// Counters::error after a run
+int device_error(uint64_t code) {
+  std::fprintf(stderr, "bsgpu: device sanity check failed (code %llu)\n", (unsigned long long)code);
+  return BSG_EDEVICE;
+}
+
 }  // namespace
 
 struct bsg_engine {
@@ -378,8 +436,6 @@ struct bsg_engine {
   const uint8_t* d_data = nullptr;
   std::vector<StreamDesc> descs;
   Params p{};
-  uint64_t nstrips = 0, cand_cap = 0, chunk_cap = 0;
-  uint64_t data_span = 1;  // bytes from d_data to the end of the last stream (k_sha regions)
   uint64_t retry_cap = 0;  // exact candidate capacity after an overflow (one re-run)
   uint32_t nstreams = 0;
   bool enqueued = false;
@@ -417,209 +473,342 @@ struct bsg_engine {
 
   int setdev() { return herr(hipSetDevice(dev)); }
 
-  int enqueue() {
-    const uint32_t ns = nstreams;
-    if (early_open) {  // a failed run left second-stream work its engine stream never waited for
-      HCHECK(hipStreamSynchronize(estream));
-      early_open = false;
-    }
-    // strips
-    std::vector<uint64_t> s0(ns + 1);
-    uint64_t strips = 0, total_len = 0, chunk_bound = 0;
-    data_span = 1;
-    for (uint32_t s = 0; s < ns; ++s) {
-      descs[s].strip0 = strips;
-      s0[s] = strips;
-      strips += (descs[s].len + kStrip - 1) / kStrip;
-      total_len += descs[s].len;
-      data_span = std::max<uint64_t>(data_span, descs[s].data_off + descs[s].len);
+  RunPlan plan_split() {
+    RunPlan pl;
+    pl.scan = true;
+    pl.ns = nstreams;
+    uint64_t chunk_bound = 0;
+    for (uint32_t s = 0; s < pl.ns; ++s) {
+      descs[s].strip0 = pl.strips;
+      pl.strips += (descs[s].len + kStrip - 1) / kStrip;
+      pl.total_len += descs[s].len;
+      pl.data_span = std::max<uint64_t>(pl.data_span, descs[s].data_off + descs[s].len);
       chunk_bound += (descs[s].len + (descs[s].seg_base - descs[s].open_start)) / p.min_size + 2;
     }
-    s0[ns] = strips;
-    nstrips = strips;
     {
       // random input yields ~len/2^bits candidates; degenerate input (e.g. all zeros: one per
       // byte) overflows this estimate and is re-run once at its exact size by finish().
       const uint32_t b = std::min<uint32_t>(p.split_bits, 16);
-      cand_cap = std::max<uint64_t>(1u << 16, ((total_len >> b) << 2) + 2ull * ns + 1024);
-      if (retry_cap > cand_cap) cand_cap = retry_cap;
+      pl.cand_cap = std::max<uint64_t>(1u << 16, ((pl.total_len >> b) << 2) + 2ull * pl.ns + 1024);
+      if (retry_cap > pl.cand_cap) pl.cand_cap = retry_cap;
     }
     // Every chunk ends at a candidate (the forced final one included), and a run whose
     // candidates overflow cand_cap selects nothing, so cand_cap also bounds the chunk count; it
     // is the tighter bound for small MinSize (len / MinSize records would be ~len for MinSize 1).
-    chunk_cap = std::min(chunk_bound, cand_cap);
-    HCHECK(streams.ensure(sizeof(StreamDesc) * (ns ? ns : 1)));
-    HCHECK(strip0.ensure(sizeof(uint64_t) * (ns + 1)));
-    HCHECK(counts.ensure(sizeof(uint32_t) * (strips ? strips : 1)));
-    // the refine lists (one per k_scan workgroup, scan_list_cap entries each), then their
-    // lengths (u32 per list)
-    const uint32_t lists = strips ? scan_lists(strips, num_cus) : 0;
-    const uint64_t list_cap = scan_list_cap(strips, lists);
-    HCHECK(refine.ensure(sizeof(uint64_t) * (lists * list_cap + 1) + sizeof(uint32_t) * (lists + 1)));
-    HCHECK(slots.ensure(sizeof(uint32_t) * kSlotCap * (strips ? strips : 1)));
-    HCHECK(strip_off.ensure(sizeof(uint64_t) * (strips ? strips : 1)));
-    HCHECK(partials_a.ensure(sizeof(uint64_t) * prefix_partials_needed(strips)));
-    HCHECK(partials_b.ensure(sizeof(uint64_t) * prefix_partials_needed(cand_cap)));
-    HCHECK(cand.ensure(sizeof(uint64_t) * cand_cap));
-    HCHECK(flags.ensure(sizeof(uint32_t) * cand_cap));
-    HCHECK(fidx.ensure(sizeof(uint64_t) * cand_cap));
-    HCHECK(bnd_end.ensure(sizeof(uint64_t) * chunk_cap));
-    HCHECK(bnd_info.ensure(sizeof(uint64_t) * chunk_cap));
-    HCHECK(out.ensure(sizeof(ChunkRec) * chunk_cap));
-    HCHECK(scount.ensure(sizeof(uint64_t) * (ns ? ns : 1)));
-    HCHECK(last_end.ensure(sizeof(uint64_t) * (ns ? ns : 1)));
-    HCHECK(carry.ensure(sizeof(CarryOut) * (ns ? ns : 1)));
-    HCHECK(ctr.ensure(sizeof(Counters) + sizeof(Early)));
-    HCHECK(long_list.ensure(sizeof(uint64_t) * (chunk_cap + ns)));
-    HCHECK(order.ensure(sizeof(uint64_t) * (chunk_cap + ns)));
-    HCHECK(jinfo.ensure(sizeof(uint32_t) * (chunk_cap + ns)));
-    HCHECK(jdesc.ensure(sizeof(LaneJob) * (chunk_cap + ns)));
+    pl.chunk_cap = std::min(chunk_bound, pl.cand_cap);
+    // the refine lists: one per k_scan workgroup, scan_list_cap entries each
+    pl.lists = pl.strips ? scan_lists(pl.strips, num_cus) : 0;
+    pl.list_cap = scan_list_cap(pl.strips, pl.lists);
+    pl.jobs = pl.chunk_cap + pl.ns;
+    pl.early = early_ok() && pl.total_len >= early_min && pl.strips;
+    pl.light = pl.early && pl.total_len <= (uint64_t)knob(BSG_KNOB_LIGHT_BYTES).load();
+    return pl;
+  }
+
+  // bsg_engine_hash: one final chunk per stream, no candidates
+  RunPlan plan_hash() {
+    RunPlan pl;
+    pl.ns = nstreams;
+    for (uint32_t s = 0; s < pl.ns; ++s)
+      pl.data_span = std::max<uint64_t>(pl.data_span, descs[s].data_off + descs[s].len);
+    pl.chunk_cap = pl.ns;
+    pl.jobs = pl.chunk_cap + pl.ns;
+    return pl;
+  }
+
+  // The Early record lives after the Counters in `ctr`, so k_start clears both at once; a hash
+  // run has no early chains and keeps (and clears) the Counters alone.
+  static size_t ctr_bytes(const RunPlan& pl) {
+    return sizeof(Counters) + (pl.scan ? sizeof(Early) : 0);
+  }
+
+  // Every work buffer at the size the plan needs (a buffer only ever grows).
+  int reserve(const RunPlan& pl) {
+    const uint64_t nn = pl.ns ? pl.ns : 1;
+    // a hash run sizes its records and jobs for one blob at least (an empty batch)
+    const uint64_t recs = pl.scan ? pl.chunk_cap : nn;
+    const uint64_t jobs = pl.scan ? pl.jobs : 2 * nn;
+    if (pl.scan) {
+      const uint64_t st = pl.strips ? pl.strips : 1;
+      HCHECK(strip0.ensure(sizeof(uint64_t) * (pl.ns + 1)));
+      HCHECK(counts.ensure(sizeof(uint32_t) * st));
+      // the refine lists, then their lengths (u32 per list)
+      HCHECK(refine.ensure(sizeof(uint64_t) * (pl.lists * pl.list_cap + 1) +
+                           sizeof(uint32_t) * (pl.lists + 1)));
+      HCHECK(slots.ensure(sizeof(uint32_t) * kSlotCap * st));
+      HCHECK(strip_off.ensure(sizeof(uint64_t) * st));
+      HCHECK(partials_a.ensure(sizeof(uint64_t) * prefix_partials_needed(pl.strips)));
+      HCHECK(partials_b.ensure(sizeof(uint64_t) * prefix_partials_needed(pl.cand_cap)));
+      HCHECK(cand.ensure(sizeof(uint64_t) * pl.cand_cap));
+      HCHECK(flags.ensure(sizeof(uint32_t) * pl.cand_cap));
+      HCHECK(fidx.ensure(sizeof(uint64_t) * pl.cand_cap));
+      HCHECK(h_strip0.ensure(sizeof(uint64_t) * (pl.ns + 1)));
+    }
+    HCHECK(streams.ensure(sizeof(StreamDesc) * nn));
+    HCHECK(bnd_end.ensure(sizeof(uint64_t) * recs));
+    HCHECK(bnd_info.ensure(sizeof(uint64_t) * recs));
+    HCHECK(out.ensure(sizeof(ChunkRec) * recs));
+    HCHECK(scount.ensure(sizeof(uint64_t) * nn));
+    HCHECK(last_end.ensure(sizeof(uint64_t) * nn));
+    HCHECK(carry.ensure(sizeof(CarryOut) * nn));
+    HCHECK(ctr.ensure(ctr_bytes(pl)));
+    HCHECK(long_list.ensure(sizeof(uint64_t) * jobs));
+    HCHECK(order.ensure(sizeof(uint64_t) * jobs));
+    HCHECK(jinfo.ensure(sizeof(uint32_t) * jobs));
+    HCHECK(jdesc.ensure(sizeof(LaneJob) * jobs));
     HCHECK(regions.ensure(sizeof(Regions)));
-    HCHECK(oreg.ensure(chunk_cap + ns));
-    HCHECK(rorder.ensure(sizeof(uint64_t) * (chunk_cap + ns)));
+    HCHECK(oreg.ensure(jobs));
+    HCHECK(rorder.ensure(sizeof(uint64_t) * jobs));
     HCHECK(buckets.ensure(sizeof(uint32_t) * 4 * kLptBuckets));
-    HCHECK(h_streams.ensure(sizeof(StreamDesc) * (ns ? ns : 1)));
-    HCHECK(h_strip0.ensure(sizeof(uint64_t) * (ns + 1)));
+    HCHECK(h_streams.ensure(sizeof(StreamDesc) * nn));
     HCHECK(h_ctr.ensure(sizeof(Counters)));
+    return BSG_OK;
+  }
 
+  Counters* dctr() const { return ctr.as<Counters>(); }
+  Early* dearly() const { return reinterpret_cast<Early*>(ctr.as<uint8_t>() + sizeof(Counters)); }
+
+  // k_start reads the descriptors (and a split run's first strips) from pinned host memory
+  StartArgs start_args(const RunPlan& pl) const {
+    StartArgs a{};
+    a.src = static_cast<const StreamDesc*>(h_streams.dev());
+    a.streams = streams.as<StreamDesc>();
+    a.nstreams = pl.ns;
+    a.last_end = last_end.as<uint64_t>();
+    a.scount = scount.as<uint64_t>();
+    a.carry = carry.as<CarryOut>();
+    a.zero0 = ctr.as<uint32_t>();
+    a.nzero0 = (uint32_t)(ctr_bytes(pl) / 4);
+    a.zero1 = buckets.as<uint32_t>();
+    a.nzero1 = 2 * kLptBuckets;
+    if (pl.scan) {
+      a.src_strip0 = static_cast<const uint64_t*>(h_strip0.dev());
+      a.strip0 = strip0.as<uint64_t>();
+      a.zero2 = partials_a.as<uint32_t>();
+      a.nzero2 = (uint32_t)(2 * prefix_partials_needed(pl.strips));
+      a.zero3 = partials_b.as<uint32_t>();
+      a.nzero3 = (uint32_t)(2 * prefix_partials_needed(pl.cand_cap));
+    }
+    return a;
+  }
+
+  ScanArgs scan_args(const RunPlan& pl) const {
+    ScanArgs a{};
+    a.data = d_data;
+    a.streams = streams.as<StreamDesc>();
+    a.strip0 = strip0.as<uint64_t>();
+    a.nstreams = pl.ns;
+    a.nstrips = pl.strips;
+    a.table = table.as<uint32_t>();
+    a.p = p;
+    a.counts = counts.as<uint32_t>();
+    a.refine = refine.as<uint64_t>();
+    a.slots = slots.as<uint32_t>();
+    a.cand_off = strip_off.as<uint64_t>();
+    a.cand = cand.as<uint64_t>();
+    a.cand_cap = pl.cand_cap;
+    a.ctr = dctr();
+    a.lists = pl.lists;
+    a.list_cap = pl.list_cap;
+    a.list_cnt = reinterpret_cast<uint32_t*>(refine.as<uint64_t>() + pl.lists * pl.list_cap + 1);
+    return a;
+  }
+
+  // a hash run has no candidates: k_blob_jobs writes one final chunk per stream
+  ChunkArgs chunk_args(const RunPlan& pl) const {
+    ChunkArgs a{};
+    if (pl.scan) {
+      a.cand = cand.as<uint64_t>();
+      a.flags = flags.as<uint32_t>();
+      a.fidx = fidx.as<uint64_t>();
+    }
+    a.bnd_end = bnd_end.as<uint64_t>();
+    a.bnd_info = bnd_info.as<uint64_t>();
+    a.scount = scount.as<uint64_t>();
+    a.last_end = last_end.as<uint64_t>();
+    a.chunk_cap = pl.chunk_cap;
+    a.p = p;
+    a.ctr = dctr();
+    a.streams = streams.as<StreamDesc>();
+    return a;
+  }
+
+  // k_lens .. k_sha and the early chains; `early`: this run's Early record, or nullptr
+  ShaArgs sha_args(const RunPlan& pl, int long_mode, Early* early) const {
+    ShaArgs a{};
+    a.data = d_data;
+    a.streams = streams.as<StreamDesc>();
+    a.nstreams = pl.ns;
+    a.bnd_end = bnd_end.as<uint64_t>();
+    a.bnd_info = bnd_info.as<uint64_t>();
+    a.last_end = last_end.as<uint64_t>();
+    a.ctr = dctr();
+    a.out = out.as<ChunkRec>();
+    a.carry = carry.as<CarryOut>();
+    a.chunk_cap = pl.chunk_cap;
+    a.long_list = long_list.as<uint64_t>();
+    a.order = order.as<uint64_t>();
+    a.bucket_cnt = buckets.as<uint32_t>();
+    a.bucket_elig = buckets.as<uint32_t>() + kLptBuckets;
+    a.bucket_off = buckets.as<uint32_t>() + 2 * kLptBuckets;
+    a.bucket_loff = buckets.as<uint32_t>() + 3 * kLptBuckets;
+    a.jinfo = jinfo.as<uint32_t>();
+    a.jdesc = jdesc.as<LaneJob>();
+    a.reg = regions.as<Regions>();
+    a.oreg = oreg.as<uint8_t>();
+    a.rorder = pl.data_span > kRegionBytes ? rorder.as<uint64_t>() : order.as<uint64_t>();
+    a.span = pl.data_span;
+    a.long_mode = long_mode;
+    a.waves = 4u * (uint32_t)num_cus;
+    a.seq_wait_limit = seq_wait_limit();
+    a.cand = pl.scan ? cand.as<uint64_t>() : nullptr;
+    a.early = early;
+    return a;
+  }
+
+  // descriptors in, counters and bucket counts zeroed, streams initialised: one dispatch
+  int run_start(const RunPlan& pl, hipStream_t s) {
     // The pinned staging of the previous run may still be in flight: finish() synchronised.
-    std::memcpy(h_streams.p, descs.data(), sizeof(StreamDesc) * ns);
-    std::memcpy(h_strip0.p, s0.data(), sizeof(uint64_t) * (ns + 1));
-    {  // descriptors in, counters and bucket counts zeroed, streams initialised: one dispatch
-      const auto* hs = static_cast<const StreamDesc*>(h_streams.dev());
-      const auto* h0 = static_cast<const uint64_t*>(h_strip0.dev());
-      if (!hs || !h0) return BSG_EDEVICE;
-      StartArgs st{hs, h0, streams.as<StreamDesc>(), strip0.as<uint64_t>(), ns,
-                   last_end.as<uint64_t>(), scount.as<uint64_t>(), carry.as<CarryOut>(),
-                   ctr.as<uint32_t>(), (uint32_t)((sizeof(Counters) + sizeof(Early)) / 4),
-                   buckets.as<uint32_t>(), 2 * kLptBuckets,
-                   partials_a.as<uint32_t>(), (uint32_t)(2 * prefix_partials_needed(strips)),
-                   partials_b.as<uint32_t>(), (uint32_t)(2 * prefix_partials_needed(cand_cap))};
-      HCHECK(dbg("launch_start", stream, launch_start(st, stream)));
+    std::memcpy(h_streams.p, descs.data(), sizeof(StreamDesc) * pl.ns);
+    if (pl.scan) {
+      uint64_t* h0 = h_strip0.as<uint64_t>();
+      for (uint32_t k = 0; k < pl.ns; ++k) h0[k] = descs[k].strip0;
+      h0[pl.ns] = pl.strips;
     }
-    Counters* dctr = ctr.as<Counters>();
-    Early* dearly = reinterpret_cast<Early*>(ctr.as<uint8_t>() + sizeof(Counters));
-    const bool early = early_ok() && total_len >= early_min && strips;
-    if (early) {
-      if (!estream) HCHECK(stream_acquire(dev, &estream));
-      // device-side dependencies only: no system-scope release (an L2 write-back) at record
-      const unsigned fl = hipEventDisableTiming | hipEventDisableSystemFence;
-      if (!cand_ev) HCHECK(hipEventCreateWithFlags(&cand_ev, fl));
-      if (!pick_ev) HCHECK(hipEventCreateWithFlags(&pick_ev, fl));
-      if (!early_ev) HCHECK(hipEventCreateWithFlags(&early_ev, fl));
-    }
-    ShaArgs sh{d_data, streams.as<StreamDesc>(), ns, bnd_end.as<uint64_t>(),
-               bnd_info.as<uint64_t>(), last_end.as<uint64_t>(), dctr, out.as<ChunkRec>(),
-               carry.as<CarryOut>(), chunk_cap, long_list.as<uint64_t>(), order.as<uint64_t>(),
-               buckets.as<uint32_t>(), buckets.as<uint32_t>() + kLptBuckets,
-               buckets.as<uint32_t>() + 2 * kLptBuckets, buckets.as<uint32_t>() + 3 * kLptBuckets,
-               jinfo.as<uint32_t>(), jdesc.as<LaneJob>(), regions.as<Regions>(), oreg.as<uint8_t>(),
-               data_span > kRegionBytes ? rorder.as<uint64_t>() : order.as<uint64_t>(), data_span,
-               long_mode(), 4u * (uint32_t)num_cus, seq_wait_limit(), cand.as<uint64_t>(),
-               early ? dearly : nullptr};
+    const StartArgs st = start_args(pl);
+    if (!st.src || (pl.scan && !st.src_strip0)) return BSG_EDEVICE;
+    HCHECK(dbg("launch_start", s, launch_start(st, s)));
+    return BSG_OK;
+  }
 
-    ScanArgs sa{};
-    sa.data = d_data;
-    sa.streams = streams.as<StreamDesc>();
-    sa.strip0 = strip0.as<uint64_t>();
-    sa.nstreams = ns;
-    sa.nstrips = strips;
-    sa.table = table.as<uint32_t>();
-    sa.p = p;
-    sa.counts = counts.as<uint32_t>();
-    sa.refine = refine.as<uint64_t>();
-    sa.slots = slots.as<uint32_t>();
-    sa.cand_off = strip_off.as<uint64_t>();
-    sa.cand = cand.as<uint64_t>();
-    sa.cand_cap = cand_cap;
-    sa.ctr = dctr;
-    sa.lists = lists;
-    sa.list_cap = list_cap;
-    sa.list_cnt = reinterpret_cast<uint32_t*>(refine.as<uint64_t>() + lists * list_cap + 1);
+  // the second stream and the events of the early chains, at the engine's first run with them
+  int early_prepare() {
+    if (!estream) HCHECK(stream_acquire(dev, &estream));
+    // device-side dependencies only: no system-scope release (an L2 write-back) at record
+    const unsigned fl = hipEventDisableTiming | hipEventDisableSystemFence;
+    if (!cand_ev) HCHECK(hipEventCreateWithFlags(&cand_ev, fl));
+    if (!pick_ev) HCHECK(hipEventCreateWithFlags(&pick_ev, fl));
+    if (!early_ev) HCHECK(hipEventCreateWithFlags(&early_ev, fl));
+    return BSG_OK;
+  }
+
+  // k_scan, the candidate offsets, k_compact: the sorted candidates of the run
+  int run_scan(const RunPlan& pl, hipStream_t s) {
+    const ScanArgs sa = scan_args(pl);
     mark(0);
     // k_scan: the fast pass, then each workgroup's exact pass over its own refine list
-    if (strips) HCHECK(dbg("launch_scan", stream, launch_scan(sa, stream, num_cus)));
+    if (pl.strips) HCHECK(dbg("launch_scan", s, launch_scan(sa, s, num_cus)));
     mark(1);
 
     PrefixArgs pa{};
     pa.in = counts.as<uint32_t>();
     pa.out = strip_off.as<uint64_t>();
     pa.partials = partials_a.as<uint64_t>();
-    pa.n_bound = strips;
-    pa.n_dev = nullptr;
-    pa.total = &dctr->ncand;
-    pa.overflow = &dctr->overflow;
-    pa.cap = cand_cap;
-    pa.skip_if = nullptr;
-    pa.error = &dctr->error;
-    HCHECK(dbg("launch_prefix", stream, launch_prefix(pa, stream)));
+    pa.n_bound = pl.strips;
+    pa.total = &dctr()->ncand;
+    pa.overflow = &dctr()->overflow;
+    pa.cap = pl.cand_cap;
+    pa.error = &dctr()->error;
+    HCHECK(dbg("launch_prefix", s, launch_prefix(pa, s)));
 
-    if (strips) HCHECK(dbg("launch_compact", stream, launch_compact(sa, stream, num_cus)));
+    if (pl.strips) HCHECK(dbg("launch_compact", s, launch_compact(sa, s, num_cus)));
     // (exits at once unless a strip had more candidates than slots; k_pick needs them all)
-    if (strips) HCHECK(dbg("launch_rescan", stream, launch_rescan(sa, stream, num_cus)));
-    const bool light = early && total_len <= (uint64_t)knob(BSG_KNOB_LIGHT_BYTES).load();
-    hipStream_t sel_stream = stream;  // where selection and k_sha run
-    if (early && light) {  // chains on the engine stream, selection beside them
-      HCHECK(dbg("launch_pick", stream,
-                 launch_pick(cand.as<uint64_t>(), cand_cap, dctr, p.min_size, dearly, stream,
-                             num_cus)));
-      HCHECK(hipEventRecord(pick_ev, stream));
-      HCHECK(dbg("launch_early", stream, launch_early(sh, p.split_bits, stream)));
+    if (pl.strips) HCHECK(dbg("launch_rescan", s, launch_rescan(sa, s, num_cus)));
+    return BSG_OK;
+  }
+
+  // k_pick and k_early on stream s
+  int run_pick(const RunPlan& pl, const ShaArgs& sh, hipStream_t s) {
+    HCHECK(dbg("launch_pick", s,
+               launch_pick(cand.as<uint64_t>(), pl.cand_cap, dctr(), p.min_size, dearly(), s,
+                           num_cus)));
+    HCHECK(hipEventRecord(pick_ev, s));
+    HCHECK(dbg("launch_early", s, launch_early(sh, p.split_bits, s)));
+    return BSG_OK;
+  }
+
+  // The early chains beside selection; *sel_stream: where selection and k_sha then run.
+  int run_early(const RunPlan& pl, const ShaArgs& sh, hipStream_t* sel_stream) {
+    int rc;
+    if (pl.light) {  // chains on the engine stream, selection beside them
+      if ((rc = run_pick(pl, sh, stream))) return rc;
       HCHECK(hipStreamWaitEvent(estream, pick_ev, 0));
-      sel_stream = estream;
+      *sel_stream = estream;
       early_open = true;  // until the engine stream waits for the selection stream's end
-    } else if (early) {  // the sorted candidates are final: pick and start two chains beside selection
+    } else {  // the sorted candidates are final: pick and start two chains beside selection
       HCHECK(hipEventRecord(cand_ev, stream));
       HCHECK(hipStreamWaitEvent(estream, cand_ev, 0));
-      HCHECK(dbg("launch_pick", estream,
-                 launch_pick(cand.as<uint64_t>(), cand_cap, dctr, p.min_size, dearly, estream,
-                             num_cus)));
-      HCHECK(hipEventRecord(pick_ev, estream));
-      HCHECK(dbg("launch_early", estream, launch_early(sh, p.split_bits, estream)));
+      if ((rc = run_pick(pl, sh, estream))) return rc;
       HCHECK(hipEventRecord(early_ev, estream));
       early_open = true;
     }
-    SelArgs sel{cand.as<uint64_t>(), streams.as<StreamDesc>(), flags.as<uint32_t>(), p, dctr};
-    HCHECK(dbg("launch_select", sel_stream, launch_select(sel, cand_cap, sel_stream, num_cus)));
+    return BSG_OK;
+  }
+
+  // k_select, the chunk indices, k_chunks (and the streaming pipeline's snapshot)
+  int run_select(const RunPlan& pl, hipStream_t s) {
+    SelArgs sel{cand.as<uint64_t>(), streams.as<StreamDesc>(), flags.as<uint32_t>(), p, dctr()};
+    HCHECK(dbg("launch_select", s, launch_select(sel, pl.cand_cap, s, num_cus)));
 
     PrefixArgs pf{};
     pf.in = flags.as<uint32_t>();
     pf.out = fidx.as<uint64_t>();
     pf.partials = partials_b.as<uint64_t>();
-    pf.n_bound = cand_cap;
-    pf.n_dev = &dctr->ncand;
-    pf.total = &dctr->nchunks;
-    pf.overflow = nullptr;
-    pf.cap = 0;
-    pf.skip_if = &dctr->overflow;
-    pf.error = &dctr->error;
-    HCHECK(dbg("launch_prefix", sel_stream, launch_prefix(pf, sel_stream)));
+    pf.n_bound = pl.cand_cap;
+    pf.n_dev = &dctr()->ncand;
+    pf.total = &dctr()->nchunks;
+    pf.skip_if = &dctr()->overflow;
+    pf.error = &dctr()->error;
+    HCHECK(dbg("launch_prefix", s, launch_prefix(pf, s)));
 
-    ChunkArgs ca{cand.as<uint64_t>(), flags.as<uint32_t>(), fidx.as<uint64_t>(),
-                 bnd_end.as<uint64_t>(), bnd_info.as<uint64_t>(), scount.as<uint64_t>(),
-                 last_end.as<uint64_t>(), chunk_cap, p, dctr, streams.as<StreamDesc>()};
-    HCHECK(dbg("launch_chunks", sel_stream, launch_chunks(ca, cand_cap, ns, sel_stream, num_cus)));
+    HCHECK(dbg("launch_chunks", s, launch_chunks(chunk_args(pl), pl.cand_cap, pl.ns, s, num_cus)));
     if (snapshot) {  // by kernel, not by the copy engine (see launch_copy_out)
-      HCHECK(h_snap.ensure(sizeof(Counters) + 8ull * (ns ? ns : 1)));
+      HCHECK(h_snap.ensure(sizeof(Counters) + 8ull * (pl.ns ? pl.ns : 1)));
       if (!sel_ev) HCHECK(hipEventCreateWithFlags(&sel_ev, hipEventDisableTiming));
       uint8_t* hs = static_cast<uint8_t*>(h_snap.dev());
       if (!hs) return BSG_EDEVICE;
       HCHECK(launch_copy_out(ctr.p, hs, sizeof(Counters), stream));
-      if (ns) HCHECK(launch_copy_out(last_end.p, hs + sizeof(Counters), 8ull * ns, stream));
+      if (pl.ns) HCHECK(launch_copy_out(last_end.p, hs + sizeof(Counters), 8ull * pl.ns, stream));
       HCHECK(hipEventRecord(sel_ev, stream));
     }
+    return BSG_OK;
+  }
 
-    if (early && !light) HCHECK(hipStreamWaitEvent(stream, pick_ev, 0));  // k_lens reads the picks
-    HCHECK(dbg("launch_longlist", sel_stream, launch_longlist(sh, chunk_cap + ns, sel_stream, num_cus)));
-    mark(2, sel_stream);
-    HCHECK(dbg("launch_sha", sel_stream, launch_sha(sh, chunk_cap + ns, sel_stream, num_cus)));
-    if (early && light) HCHECK(hipEventRecord(early_ev, estream));  // selection + k_sha done
-    if (early) {  // the early chains' records into place, once they (and k_sha) are done
-      HCHECK(hipStreamWaitEvent(stream, early_ev, 0));
-      early_open = false;  // the engine stream now orders everything after the chains
-      HCHECK(dbg("launch_early_fix", stream, launch_early_fix(dearly, out.as<ChunkRec>(), dctr,
-                                                              stream)));
+  // the job lists (k_lens .. k_order), then k_sha
+  int run_sha(const RunPlan& pl, const ShaArgs& sh, hipStream_t s) {
+    HCHECK(dbg("launch_longlist", s, launch_longlist(sh, pl.jobs, s, num_cus)));
+    mark(2, s);
+    HCHECK(dbg("launch_sha", s, launch_sha(sh, pl.jobs, s, num_cus)));
+    return BSG_OK;
+  }
+
+  // the early chains' records into place, once they (and k_sha) are done
+  int run_early_fix(const RunPlan& pl) {
+    if (pl.light) HCHECK(hipEventRecord(early_ev, estream));  // selection + k_sha done
+    HCHECK(hipStreamWaitEvent(stream, early_ev, 0));
+    early_open = false;  // the engine stream now orders everything after the chains
+    HCHECK(dbg("launch_early_fix", stream,
+               launch_early_fix(dearly(), out.as<ChunkRec>(), dctr(), stream)));
+    return BSG_OK;
+  }
+
+  int enqueue() {
+    int rc;
+    if (early_open) {  // a failed run left second-stream work its engine stream never waited for
+      HCHECK(hipStreamSynchronize(estream));
+      early_open = false;
     }
+    const RunPlan pl = plan_split();
+    if ((rc = reserve(pl)) || (rc = run_start(pl, stream))) return rc;
+    if (pl.early && (rc = early_prepare())) return rc;
+    const ShaArgs sh = sha_args(pl, long_mode(), pl.early ? dearly() : nullptr);
+    if ((rc = run_scan(pl, stream))) return rc;
+    hipStream_t sel_stream = stream;  // where selection and k_sha run
+    if (pl.early && (rc = run_early(pl, sh, &sel_stream))) return rc;
+    if ((rc = run_select(pl, sel_stream))) return rc;
+    if (pl.early && !pl.light) HCHECK(hipStreamWaitEvent(stream, pick_ev, 0));  // k_lens reads the picks
+    if ((rc = run_sha(pl, sh, sel_stream))) return rc;
+    if (pl.early && (rc = run_early_fix(pl))) return rc;
     mark(3);
     enqueued = true;
     return BSG_OK;
@@ -627,63 +816,18 @@ struct bsg_engine {
 
   // bsg_engine_hash: every stream is one blob, hashed whole (Blob.Ref of many blobs): no scan or
   // selection, one final chunk per stream, then the same job ordering and k_sha as a split run.
+  // (No candidates, so such a run cannot overflow: finish() never re-runs it.)
   int enqueue_hash() {
-    const uint32_t ns = nstreams;
-    data_span = 1;
-    for (uint32_t s = 0; s < ns; ++s)
-      data_span = std::max<uint64_t>(data_span, descs[s].data_off + descs[s].len);
-    nstrips = 0;
-    cand_cap = 0;
-    chunk_cap = ns;
-    const uint64_t nn = ns ? ns : 1;
-    HCHECK(streams.ensure(sizeof(StreamDesc) * nn));
-    HCHECK(bnd_end.ensure(sizeof(uint64_t) * nn));
-    HCHECK(bnd_info.ensure(sizeof(uint64_t) * nn));
-    HCHECK(out.ensure(sizeof(ChunkRec) * nn));
-    HCHECK(scount.ensure(sizeof(uint64_t) * nn));
-    HCHECK(last_end.ensure(sizeof(uint64_t) * nn));
-    HCHECK(carry.ensure(sizeof(CarryOut) * nn));
-    HCHECK(ctr.ensure(sizeof(Counters)));
-    HCHECK(long_list.ensure(sizeof(uint64_t) * 2 * nn));
-    HCHECK(order.ensure(sizeof(uint64_t) * 2 * nn));
-    HCHECK(jinfo.ensure(sizeof(uint32_t) * 2 * nn));
-    HCHECK(jdesc.ensure(sizeof(LaneJob) * 2 * nn));
-    HCHECK(regions.ensure(sizeof(Regions)));
-    HCHECK(oreg.ensure(2 * nn));
-    HCHECK(rorder.ensure(sizeof(uint64_t) * 2 * nn));
-    HCHECK(buckets.ensure(sizeof(uint32_t) * 4 * kLptBuckets));
-    HCHECK(h_streams.ensure(sizeof(StreamDesc) * nn));
-    HCHECK(h_ctr.ensure(sizeof(Counters)));
-    std::memcpy(h_streams.p, descs.data(), sizeof(StreamDesc) * ns);
-    {
-      const auto* hs = static_cast<const StreamDesc*>(h_streams.dev());
-      if (!hs) return BSG_EDEVICE;
-      StartArgs st{hs, nullptr, streams.as<StreamDesc>(), nullptr, ns, last_end.as<uint64_t>(),
-                   scount.as<uint64_t>(), carry.as<CarryOut>(), ctr.as<uint32_t>(),
-                   (uint32_t)(sizeof(Counters) / 4), buckets.as<uint32_t>(), 2 * kLptBuckets,
-                   nullptr, 0, nullptr, 0};
-      HCHECK(dbg("launch_start", stream, launch_start(st, stream)));
-    }
-    Counters* dctr = ctr.as<Counters>();
+    int rc;
+    const RunPlan pl = plan_hash();
+    if ((rc = reserve(pl)) || (rc = run_start(pl, stream))) return rc;
     mark(0);
     mark(1);  // no scan / selection stage
-    ChunkArgs ca{nullptr, nullptr, nullptr, bnd_end.as<uint64_t>(), bnd_info.as<uint64_t>(),
-                 scount.as<uint64_t>(), last_end.as<uint64_t>(), chunk_cap, p, dctr,
-                 streams.as<StreamDesc>()};
-    if (ns) HCHECK(dbg("launch_blob_jobs", stream,
-                       launch_blob_jobs(ca, streams.as<StreamDesc>(), ns, stream, num_cus)));
-    ShaArgs sh{d_data, streams.as<StreamDesc>(), ns, bnd_end.as<uint64_t>(),
-               bnd_info.as<uint64_t>(), last_end.as<uint64_t>(), dctr, out.as<ChunkRec>(),
-               carry.as<CarryOut>(), chunk_cap, long_list.as<uint64_t>(), order.as<uint64_t>(),
-               buckets.as<uint32_t>(), buckets.as<uint32_t>() + kLptBuckets,
-               buckets.as<uint32_t>() + 2 * kLptBuckets, buckets.as<uint32_t>() + 3 * kLptBuckets,
-               jinfo.as<uint32_t>(), jdesc.as<LaneJob>(), regions.as<Regions>(), oreg.as<uint8_t>(),
-               data_span > kRegionBytes ? rorder.as<uint64_t>() : order.as<uint64_t>(), data_span,
-               hash_long_mode >= 0 ? hash_long_mode : long_mode(), 4u * (uint32_t)num_cus,
-               seq_wait_limit()};
-    HCHECK(dbg("launch_longlist", stream, launch_longlist(sh, chunk_cap + ns, stream, num_cus)));
-    mark(2);
-    HCHECK(dbg("launch_sha", stream, launch_sha(sh, chunk_cap + ns, stream, num_cus)));
+    if (pl.ns) HCHECK(dbg("launch_blob_jobs", stream,
+                          launch_blob_jobs(chunk_args(pl), streams.as<StreamDesc>(), pl.ns, stream,
+                                           num_cus)));
+    const ShaArgs sh = sha_args(pl, hash_long_mode >= 0 ? hash_long_mode : long_mode(), nullptr);
+    if ((rc = run_sha(pl, sh, stream))) return rc;
     mark(3);
     enqueued = true;
     return BSG_OK;
@@ -702,13 +846,8 @@ struct bsg_engine {
     }
     retry_cap = 0;
     if (last.overflow) return BSG_ENOMEM;
-    if (last.error) {
-      std::fprintf(stderr, "bsgpu: device sanity check failed (code %llu)\n",
-                   (unsigned long long)last.error);
-      enqueued = false;
-      return BSG_EDEVICE;
-    }
     enqueued = false;
+    if (last.error) return device_error(last.error);
     if (profile) {
       for (int i = 0; i < 3; ++i)
         if ((profile == 2 && i < 2) ||
@@ -1052,43 +1191,60 @@ static uint64_t ns_since(std::chrono::steady_clock::time_point t0) {
              std::chrono::steady_clock::now() - t0).count();
 }
 
-struct bsg_ctx {
-  bsg_params params{};
-  Params p{};
-  int dev = 0;
-  uint32_t table[256];
-  size_t tile = 256ull << 20;
-  uint64_t carry_cap = kDefaultCarryCap;
-  int nslots = default_slots();
-  TileSlot slots[kMaxSlots];
-  int ndata = default_data_slots(nslots);
-  DataSlot data[kMaxData];
+// hipEventElapsedTime(a, b) in nanoseconds into *out, negatives as 0; *out is left alone when the
+// events have no time to give
+static bool elapsed_ns(hipEvent_t a, hipEvent_t b, uint64_t* out) {
+  float ms = 0.f;
+  if (hipEventElapsedTime(&ms, a, b) != hipSuccess) {
+    (void)hipGetLastError();
+    return false;
+  }
+  *out = ms > 0.f ? (uint64_t)((double)ms * 1e6) : 0;
+  return true;
+}
+
+// Where a context is in its current stream: everything a new stream starts over. bsg_ctx is
+// one of these plus the resources that outlive a stream, so reset() assigns a fresh value and a
+// field added here needs no second mention.
+struct StreamState {
   int dcur = 0;             // data slot of the tile the host is filling
   bool dready = false;      // the copy stream waits for data[dcur]'s previous readers already
-  hipStream_t cstream = nullptr;  // H2D copies of every tile (from the process's stream pool)
-  Stage stages[kStages];
   int cur = 0;              // slot of the tile the host is filling
   size_t fill = 0;          // bytes of the current tile (copied to the device or staged)
   int scur = 0;             // stage the host is filling
   size_t sfill = 0;         // bytes in stages[scur] (the current tile's last sfill bytes)
   int prev = -1;            // last submitted slot (its open chunk continues into `cur`)
-  std::deque<int> inflight; // submitted slots in stream order
   uint64_t pos = 0;         // stream offset of slots[cur]'s first byte
   uint64_t stream0 = 0;     // stream offset of the stream's first byte (0; bsg_set_stream_base)
-  uint8_t hist[64];         // the 64 stream bytes before pos
-  uint8_t tail[64];         // the last 64 stream bytes copied to the device so far
-  std::deque<bsg_chunk> ready;
+  uint8_t hist[64] = {};    // the 64 stream bytes before pos
+  uint8_t tail[64] = {};    // the last 64 stream bytes copied to the device so far
   bool closed = false, started = false;
   int sticky = BSG_OK;
-  // bsg_stream_stats: counters since open / reset
-  bsg_stream_stats stats{};
-  std::atomic<uint64_t> node_bytes[4] = {};
+  bsg_stream_stats stats{};  // bsg_stream_stats: counters since open / reset
+  bool span_set = false;     // span0 recorded
+  bool tail_set = false;     // tail1 recorded
+  int slast = -1;            // stage of the latest H2D
+  bool sent = false;         // the stream's first H2D is issued (first_flush())
+};
+
+struct bsg_ctx : StreamState {
+  bsg_params params{};
+  Params p{};
+  int dev = 0;
+  uint32_t table[256];
+  size_t tile = 256ull << 20;  // (tile and carry_cap are settings: they survive reset())
+  uint64_t carry_cap = kDefaultCarryCap;
+  int nslots = default_slots();
+  TileSlot slots[kMaxSlots];
+  int ndata = default_data_slots(nslots);
+  DataSlot data[kMaxData];
+  hipStream_t cstream = nullptr;  // H2D copies of every tile (from the process's stream pool)
+  Stage stages[kStages];
+  std::deque<int> inflight; // submitted slots in stream order
+  std::deque<bsg_chunk> ready;
+  std::atomic<uint64_t> node_bytes[4] = {};  // bsg_stream_stats::copy_bytes_node
   hipEvent_t span0 = nullptr;  // recorded before the first H2D of the stream
-  bool span_set = false;
   hipEvent_t tail0 = nullptr, tail1 = nullptr;  // the final tile's kernels: start, records out
-  bool tail_set = false;
-  int slast = -1;              // stage of the latest H2D
-  bool sent = false;           // the stream's first H2D is issued (first_flush())
 
   size_t stage_size() const { return std::min(tile, kStageMax); }
 
@@ -1104,8 +1260,6 @@ struct bsg_ctx {
     HCHECK(hipEventCreate(&span0));
     HCHECK(hipEventCreate(&tail0));
     HCHECK(hipEventCreate(&tail1));
-    std::memset(hist, 0, 64);
-    std::memset(tail, 0, 64);
     return ensure_slot(0);  // the first tile's engine: errors surface at bsg_open
   }
 
@@ -1173,11 +1327,8 @@ struct bsg_ctx {
   // the finished H2D of stage st into the busy time
   void harvest(Stage& st) {
     if (!st.timed) return;
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, st.t0, st.t1) == hipSuccess)
-      stats.h2d_busy_ns += (uint64_t)((double)ms * 1e6);
-    else
-      (void)hipGetLastError();
+    uint64_t ns = 0;
+    if (elapsed_ns(st.t0, st.t1, &ns)) stats.h2d_busy_ns += ns;
     st.timed = false;
   }
 
@@ -1185,24 +1336,13 @@ struct bsg_ctx {
     if (cstream) HCHECK(hipStreamSynchronize(cstream));
     for (Stage& st : stages) harvest(st);
     bsg_stream_stats s = stats;
-    if (span_set && slast >= 0) {
-      float ms = 0.f;
-      if (hipEventElapsedTime(&ms, span0, stages[slast].t1) == hipSuccess)
-        s.h2d_span_ns = (uint64_t)((double)ms * 1e6);
-      else
-        (void)hipGetLastError();
-    }
+    if (span_set && slast >= 0) elapsed_ns(span0, stages[slast].t1, &s.h2d_span_ns);
     if (tail_set) {
-      float ms = 0.f;
-      if (hipEventSynchronize(tail1) == hipSuccess &&
-          hipEventElapsedTime(&ms, tail0, tail1) == hipSuccess)
-        s.last_tile_ns = (uint64_t)((double)ms * 1e6);
+      if (hipEventSynchronize(tail1) == hipSuccess)
+        elapsed_ns(tail0, tail1, &s.last_tile_ns);
       else
         (void)hipGetLastError();
-      if (slast >= 0 && hipEventElapsedTime(&ms, stages[slast].t1, tail1) == hipSuccess)
-        s.tail_ns = ms > 0.f ? (uint64_t)((double)ms * 1e6) : 0;
-      else
-        (void)hipGetLastError();
+      if (slast >= 0) elapsed_ns(stages[slast].t1, tail1, &s.tail_ns);
     }
     for (int k = 0; k < 4; ++k) s.copy_bytes_node[k] = node_bytes[k].load();
     s.gpu_node = device_node(dev);
@@ -1285,11 +1425,7 @@ struct bsg_ctx {
     }
     HCHECK(hipEventSynchronize(t.done_ev));
     const Counters& c = *t.eng->h_ctr.as<Counters>();
-    if (c.error) {
-      std::fprintf(stderr, "bsgpu: device sanity check failed (code %llu)\n",
-                   (unsigned long long)c.error);
-      return BSG_EDEVICE;
-    }
+    if (c.error) return device_error(c.error);
     const bsg_chunk* r = t.recs.as<bsg_chunk>();
     for (uint64_t k = 0; k < t.nchunks; ++k) ready.push_back(r[k]);
     t.busy = false;
@@ -1635,8 +1771,6 @@ struct bsg_ctx {
   int reset() {
     if (cstream) HCHECK(hipStreamSynchronize(cstream));
     for (DataSlot& ds : data) ds.free_pending = false;
-    dcur = 0;
-    dready = false;
     for (int k = 0; k < nslots; ++k) {
       TileSlot& t = slots[k];
       if (t.eng) HCHECK(hipStreamSynchronize(t.eng->stream));
@@ -1656,26 +1790,10 @@ struct bsg_ctx {
       st.timed = false;
       StagePool::get().give(&st.buf);
     }
-    stats = bsg_stream_stats{};
     for (auto& b : node_bytes) b.store(0);
-    span_set = false;
-    tail_set = false;
-    slast = -1;
-    sent = false;
     inflight.clear();
     ready.clear();
-    cur = 0;
-    fill = 0;
-    scur = 0;
-    sfill = 0;
-    prev = -1;
-    stream0 = 0;
-    pos = 0;
-    std::memset(hist, 0, 64);
-    std::memset(tail, 0, 64);
-    closed = false;
-    started = false;
-    sticky = BSG_OK;
+    static_cast<StreamState&>(*this) = StreamState{};
     return BSG_OK;
   }
 
@@ -2219,25 +2337,9 @@ int bsg_stream_stats_get(bsg_ctx* c, bsg_stream_stats* out) {
   return c->get_stats(out);
 }
 
-// bsg_split_hash_batch keeps a few engines (work buffers, pinned counters) for the next call:
-// creating and freeing one per call cost ~1 ms of allocations (profiles/r03_split_hash_batch_*).
-static std::mutex g_batch_eng_mu;
-static std::vector<bsg_engine*>& batch_engines() {
-  static auto* v = new std::vector<bsg_engine*>();  // never destroyed (see ctx_pool)
-  return *v;
-}
+// bsg_split_hash_batch's engine: a pooled one (DevicePool) with the call's table, or a new one
 static bsg_engine* batch_engine_take(int device, const uint32_t* table, int* rc) {
-  bsg_engine* e = nullptr;
-  {
-    std::lock_guard<std::mutex> g(g_batch_eng_mu);
-    auto& v = batch_engines();
-    for (size_t i = 0; i < v.size(); ++i)
-      if (v[i]->dev == device) {
-        e = v[i];
-        v.erase(v.begin() + (long)i);
-        break;
-      }
-  }
+  bsg_engine* e = DevicePool<bsg_engine>::get().take(device);
   if (!e) return bsg_engine_create(device, table, rc);
   *rc = BSG_OK;
   const uint32_t* t = table ? table : kBuzhash32Seed1;
@@ -2255,11 +2357,7 @@ static bsg_engine* batch_engine_take(int device, const uint32_t* table, int* rc)
 static void batch_engine_give(bsg_engine* e, bool ok) {
   if (ok && hipSetDevice(e->dev) == hipSuccess && hipStreamSynchronize(e->stream) == hipSuccess) {
     e->retry_cap = 0;
-    std::lock_guard<std::mutex> g(g_batch_eng_mu);
-    if (batch_engines().size() < 2) {
-      batch_engines().push_back(e);
-      return;
-    }
+    if (DevicePool<bsg_engine>::get().give(e)) return;
   }
   (void)hipGetLastError();
   bsg_engine_destroy(e);
@@ -2667,44 +2765,21 @@ void bsg_hasher_free(bsg_hasher* h) {
   delete h;
 }
 
-// bsg_sha256_batch keeps a few hashers (device buffers, pinned staging, an engine) for the next
-// call instead of creating and freeing them every time.
-static std::mutex g_hasher_pool_mu;
-static std::vector<bsg_hasher*>& hasher_pool() {
-  static auto* v = new std::vector<bsg_hasher*>();  // never destroyed (see ctx_pool)
-  return *v;
-}
-
+// (hashers, with their device buffers, pinned staging and engine, are pooled: DevicePool)
 int bsg_sha256_batch(int device, const uint8_t* base, const uint64_t* off, const uint64_t* len,
                      uint32_t n, uint8_t* refs) {
   if (n && (!base || !off || !len || !refs)) return BSG_EINVAL;
   if (n == 0) return BSG_OK;
   if (device < 0 || device >= bsg_device_count()) return BSG_ENODEV;
-  bsg_hasher* h = nullptr;
-  {
-    std::lock_guard<std::mutex> g(g_hasher_pool_mu);
-    auto& v = hasher_pool();
-    for (size_t i = 0; i < v.size(); ++i)
-      if (v[i]->dev == device) {
-        h = v[i];
-        v.erase(v.begin() + (long)i);
-        break;
-      }
-  }
+  bsg_hasher* h = DevicePool<bsg_hasher>::get().take(device);
   if (!h && !(h = bsg_hasher_new(device))) return BSG_EDEVICE;
   if (hipSetDevice(device) != hipSuccess) {
     bsg_hasher_free(h);
     return BSG_EDEVICE;
   }
   const int rc = h->sum(base, off, len, n, refs);
-  {
-    std::lock_guard<std::mutex> g(g_hasher_pool_mu);
-    if (rc == BSG_OK && hasher_pool().size() < 2) {
-      hasher_pool().push_back(h);
-      h = nullptr;
-    }
-  }
-  if (h) bsg_hasher_free(h);
+  // (sum() synchronised the hasher's streams)
+  if (rc != BSG_OK || !DevicePool<bsg_hasher>::get().give(h)) bsg_hasher_free(h);
   return rc;
 }
 

@@ -35,6 +35,73 @@ def test_write_after_close_and_late_knobs(gpu):
     w.free()
 
 
+def test_reset_equals_fresh(gpu, oracle, table):
+    """bsg_reset leaves nothing of the previous stream: after stream A (at offsets past 2^40,
+    written in uneven pieces), stream B through write_window / write_commit on the same context
+    gives the oracle's chunks, which are also those of a fresh context given the same calls, and
+    the counters read zero before B's first byte. The tile set before A is a setting, not stream
+    state: it still applies, so B (3 MiB + 17 bytes) crosses three 1 MiB tile boundaries, ends
+    on a short final tile, and no host-to-device copy exceeds a 1 MiB stage."""
+    from bs_amd.synth import splitmix_array
+    L = gpu.lib()
+    n, tile = (3 << 20) + 17, 1 << 20
+    a, b = splitmix_array(4101, n), splitmix_array(4102, n)
+
+    def raw_stats(w):
+        st = gpu.StreamStats()
+        assert L.bsg_stream_stats_get(w.h, ctypes.byref(st)) == 0
+        return st
+
+    def run_b(w):
+        done = 0
+        while done < n:
+            win = w.window()
+            k = min(len(win), n - done, 700_001)
+            win[:k] = memoryview(b)[done:done + k]
+            w.commit(k)
+            done += k
+        w.close()
+        return w.drain(), raw_stats(w)
+
+    def same(ch, want, base=0):
+        assert len(ch) == len(want)
+        assert (ch["offset"] == want["offset"] + np.uint64(base)).all()
+        for f in ("len", "level", "ref"):
+            assert (ch[f] == want[f]).all(), f
+
+    w = gpu.StreamingSplitter(bits=13, min_size=256, tile=tile)
+    w.set_stream_base(1 << 40)
+    got, at = [], 0
+    for k in (1, 999_999, 64, 1 << 20, n):
+        w.write(memoryview(a)[at:at + k])
+        got.append(w.drain())
+        at += k
+    w.close()
+    got.append(w.drain())
+    same(np.concatenate(got), oracle.split(table, a, bits=13, min_size=256), base=1 << 40)
+    assert raw_stats(w).h2d_bytes == n
+
+    w.reset()
+    st = raw_stats(w)
+    for f in ("host_bytes", "host_copy_ns", "stage_wait_ns", "h2d_bytes", "h2d_copies",
+              "h2d_busy_ns", "h2d_span_ns", "last_tile_ns", "tail_ns", "src_nodes"):
+        assert getattr(st, f) == 0, f
+    assert list(st.copy_bytes_node) == [0, 0, 0, 0]
+    ch_reset, st_reset = run_b(w)
+    w.free()
+
+    fresh = gpu.StreamingSplitter(bits=13, min_size=256, tile=tile)
+    ch_fresh, st_fresh = run_b(fresh)
+    fresh.free()
+
+    want = oracle.split(table, b, bits=13, min_size=256)
+    same(ch_reset, want)                               # offsets from 0 again: the base is gone
+    same(ch_fresh, want)
+    assert st_reset.h2d_bytes == n
+    assert st_reset.h2d_copies >= -(-n // tile)        # a stage is one tile at most: >= 4 copies
+    assert st_reset.h2d_copies == st_fresh.h2d_copies
+
+
 def test_reader_missing_root(gpu):
     st = gpu.MemStore()
     with pytest.raises(gpu.BsgError) as ei:

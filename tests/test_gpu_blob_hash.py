@@ -33,6 +33,18 @@ def test_sha256_batch_engine_path(gpu):
     assert got == [hashlib.sha256(b).digest() for b in blobs]
 
 
+def test_sha256_batch_pooled_hasher_reuse(gpu):
+    """bsg_sha256_batch takes its hasher from a pool and gives it back: one blob (one blob per
+    lane), then 70 with one of 20 KiB (a small batch with a long blob: the hasher's engine, every
+    blob on a wave ticket), then none, then one again on the hasher the engine run left."""
+    rng = np.random.default_rng(21)
+    lens = [int(x) for x in rng.integers(0, 3000, 70)]
+    lens[33] = 20 << 10
+    many = [rng.integers(0, 256, ln, dtype=np.uint8).tobytes() for ln in lens]
+    for blobs in ([b"pooled"], many, [], [many[33]]):
+        assert gpu.sha256_batch(blobs) == [hashlib.sha256(b).digest() for b in blobs]
+
+
 def test_hasher_sum_ptrs_engine_and_small(gpu):
     h = gpu.Hasher()
     try:
