@@ -170,8 +170,8 @@ constexpr uint32_t kLongMinBlocks = 1024;  // never use the wave path below 64 K
 #define BSG_SOLO 16  // configs[2]: the 9th-16th longest jobs on group tickets (1.40 us per
 #endif           // block against 1.19 solo) ended 0.5 ms after the longest
 constexpr uint32_t kSolo = BSG_SOLO;  // wave mode: the kSolo longest jobs run one per wave,
-constexpr uint32_t kGroup = 8;   // the next ones kGroup per wave (one banked lane pair each)
-constexpr uint32_t kPairGroup = 32;  // then (optionally) 32 per wave, one lane pair each
+constexpr uint32_t kGroup = 8;   // the next ones kGroup per wave (one skewed octet each)
+constexpr uint32_t kPairGroup = 32;  // then (optionally) 32 per wave, one skewed lane pair each
 constexpr int kLongRow = 68;               // LDS words per K+W row (64 + pad: conflict-free b128)
 constexpr int kRingWords = 65 * kLongRow;  // per wave: 64 K+W rows + one row of ones
 constexpr int kLptBuckets = 4096;          // longest-first job order: counting sort on nblocks

@@ -1860,10 +1860,11 @@ __device__ __forceinline__ uint32_t wave_max(uint32_t v) {
 }
 
 // Wave mode: ticket t of the long list (LPT order). Tickets [0, kSolo) are one job each, the
-// rest kGroup consecutive jobs each. The wave expands the message schedule of 64 blocks at a
-// time into its LDS ring (G chains x 64/G blocks; lane l expands block l % B of chain l / B),
-// then the skewed lane pairs of octet c (lanes 8c+2p: E, 8c+2p+1: A) run the rounds of chain
-// c, 9 VALU per round (sha256_rounds_skew); a solo job's chain is run by every pair alike.
+// next kGroup consecutive jobs each, then (pair tickets) kPairGroup each. The wave expands the
+// message schedule of 64 blocks at a time into its LDS ring (G chains x B = 64/G blocks; lane l
+// expands block l % B of chain l / B), then the B lanes of chain c run its rounds: a skewed
+// octet at 8 VALU per round (sha256_blocks_oct) for solo and group tickets, a skewed lane pair
+// at 9 (sha256_blocks_skew) for pair tickets; a solo job's chain is run by every octet alike.
 __device__ void sha_wave_job(const ShaArgs& a, uint64_t M, uint64_t t, uint64_t nlong,
                              uint32_t* ring) {
   const uint32_t lane = threadIdx.x & 63u;
@@ -2211,7 +2212,7 @@ __global__ __launch_bounds__(kShaBlock, 1) void k_sha(ShaArgs a) {
     }
   }
   if (!helper_wg) {
-    // row of ones after each wave's 64 K+W rows (the A lanes' kw in sha256_rounds_bank)
+    // row of ones after each wave's 64 K+W rows (the A lanes' kw in sha256_blocks_oct / _skew)
     for (uint32_t i = threadIdx.x & 63u; i < (uint32_t)kLongRow; i += 64) ring[64 * kLongRow + i] = 1u;
     // A plain pre-tested loop on a scalar ticket: a `for (;;) { if (lane == 0) atomic; ...;
     // break; }` form was restructured by hipcc into a nested loop that re-entered job 0 forever.

@@ -21,8 +21,13 @@ def load(name):
     return mod
 
 
+UBENCH = os.path.join(ROOT, "tools", "ubench")
+
+
 def same(tmp_path, name):
-    with open(tmp_path / name, "rb") as a, open(os.path.join(CSRC, name), "rb") as b:
+    # the single-block form is run by the microbenchmarks only and lives with them
+    where = UBENCH if name == "sha256_skew_block.inc" else CSRC
+    with open(tmp_path / name, "rb") as a, open(os.path.join(where, name), "rb") as b:
         return a.read() == b.read()
 
 

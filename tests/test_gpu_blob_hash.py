@@ -167,6 +167,62 @@ def test_engine_hash_device_resident(gpu):
         buf.free()
 
 
+@pytest.fixture(scope="module")
+def fill_boundary_blobs():
+    """Blobs whose block count nblocks = (L + 8) // 64 + 1 lands on and just past every ring-fill
+    size of k_sha: 1 | 2 (the padding spilling into a block of its own), 2 | 3 (a pair ticket's
+    fill), 8 | 9 (a group ticket's), 64 | 65 and 128 | 129 (a solo ticket's fill and a helped
+    chain's half, once and twice). With every job on wave tickets the 16 longest run solo
+    (8184 x 6, 8183 x 6, 4088 x 4) and the rest eight to a group ticket (4087 x 4 and all the
+    shorter ones: 34 jobs on 5 tickets, the last with 6 empty slots). 50 blobs, about 140 KiB;
+    expected refs from hashlib."""
+    lens = [8184] * 6 + [8183] * 6 + [4088] * 4 + [4087] * 4
+    lens += [0, 55, 56, 63, 64, 119, 120, 503, 504] * 3 + [1, 65, 127]
+    assert len(lens) == 50 and all((n + 8) // 64 + 1 <= 129 for n in lens)
+    rng = np.random.default_rng(64)
+    rng.shuffle(lens)
+    blobs = [rng.bytes(int(n)) for n in lens]
+    return blobs, [hashlib.sha256(b).digest() for b in blobs]
+
+
+@pytest.mark.parametrize("long_mode", [2, 1, 0], ids=["wave", "per_lane", "auto"])
+def test_engine_hash_fill_boundaries(gpu, fill_boundary_blobs, long_mode):
+    """The blocks that need padding and the length words, at every ring-fill boundary, through
+    k_sha's wave mode only (solo and group tickets), per-lane mode only, and the engine's own
+    choice (every blob is under the 64 KiB wave-mode floor, so per-lane again); every ref equals
+    hashlib's, and the engine's counters show that the jobs took the path the case names: all
+    50 on 16 solo + 5 group tickets, or none on any."""
+    blobs, want = fill_boundary_blobs
+    off, o = [], 0
+    for b in blobs:
+        off.append(o)
+        o = (o + len(b) + 15) & ~15
+    host = np.zeros(o + gpu.READ_SLACK, dtype=np.uint8)
+    for b, x in zip(blobs, off):
+        host[x:x + len(b)] = np.frombuffer(b, dtype=np.uint8)
+    buf = gpu.DeviceBuffer(host.size)
+    eng = gpu.Engine()
+    try:
+        buf.from_host(host)
+        with gpu.debug_knob(gpu.KNOB_LONG_MODE, long_mode):
+            eng.hash(buf.ptr, off, [len(b) for b in blobs])
+            assert eng.finish() == len(blobs)
+        ch = eng.chunks()
+        got = [bytes(r) for r in ch["ref"]]
+        bad = [(len(b), i) for i, (b, g, w) in enumerate(zip(blobs, got, want)) if g != w]
+        assert not bad, bad
+        assert list(ch["len"]) == [len(b) for b in blobs]
+        d = eng.diag()
+        print("sha path:", long_mode, d)
+        if long_mode == 2:
+            assert (d["nlong"], d["wave_tickets"]) == (len(blobs), 16 + 5), d
+        else:
+            assert (d["nlong"], d["wave_tickets"]) == (0, 0), d
+    finally:
+        eng.close()
+        buf.free()
+
+
 @pytest.fixture
 def small_windows(gpu):
     with gpu.debug_knob(gpu.KNOB_VERIFY_WINDOW, 65536):

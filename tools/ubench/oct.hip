@@ -5,7 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <cstdio>
-#include "../../bs_amd/csrc/sha256_device.h"
+#include "sha256_experiments.h"
 using namespace bsg;
 
 #define STAMP(t) asm volatile("s_memtime %0\n s_waitcnt lgkmcnt(0)" : "=s"(t) :: "memory")

@@ -5,7 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <cstdio>
-#include "../../bs_amd/csrc/sha256_device.h"
+#include "sha256_experiments.h"
 #include "skew_variants.inc"
 using namespace bsg;
 
