@@ -131,6 +131,7 @@ def lib() -> ctypes.CDLL:
         "bsg_engine_profile": (ctypes.c_int, [vp, ctypes.c_int]),
         "bsg_engine_diag": (ctypes.c_int, [vp, u64p]),
         "bsg_engine_timeline": (ctypes.c_int, [vp, u64p]),
+        "bsg_engine_tiers_debug": (ctypes.c_int, [vp, u64p]),
         "bsg_engine_stage_ms": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_float)]),
         "bsg_split_hash_batch": (ctypes.c_int, [ctypes.c_int, vp, u64p, u64p, ctypes.c_uint32,
                                                 ctypes.POINTER(Params), u32p, vp,
@@ -484,6 +485,18 @@ class Engine:
                             "clock_ghz": round(cyc / (rt * 10.0), 3),
                             "us_per_block": round(rt * 0.01 / nb, 4)}
         return out
+
+    def tiers(self) -> dict:
+        """bsg_engine_tiers_debug (test tooling, not in bsgpu.h): how k_bucket_scan split the last
+        finished run's wave-mode jobs. `nlong_grp` jobs on `tickets_grp` solo / group tickets, the
+        first `helped` of them solo chains with a helper wave; `wave_tickets` counts the pair
+        tickets too (diag()'s nlong - nlong_grp jobs). `early`: whether early chains 0 and 1
+        each hashed a chunk."""
+        d = np.zeros(6, dtype=np.uint64)
+        _check(lib().bsg_engine_tiers_debug(self.h, _p(d, ctypes.c_uint64)),
+               "bsg_engine_tiers_debug")
+        return {"nlong_grp": int(d[0]), "tickets_grp": int(d[1]), "helped": int(d[2]),
+                "wave_tickets": int(d[3]), "early": (bool(d[4]), bool(d[5]))}
 
     @property
     def candidates(self) -> int:

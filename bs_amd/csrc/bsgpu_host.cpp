@@ -2145,6 +2145,28 @@ extern "C" int bsg_engine_regions_debug(bsg_engine* e, void* out, uint64_t nbyte
   return hipMemcpy(out, e->regions.p, n, hipMemcpyDeviceToHost) == hipSuccess ? BSG_OK : BSG_EDEVICE;
 }
 
+// Test tooling (not in include/bsgpu.h): which SHA-256 path the last finished run's jobs took.
+// out[0..3]: jobs on solo / group tickets, those tickets, the solo tickets run with a helper
+// wave, all wave tickets (k_bucket_scan); out[4], out[5]: 1 if early chain 0 / 1 hashed a chunk
+// (k_pick picked one and k_lens took it out of k_sha's queues), read from the Early record
+// behind the device Counters; 0 after a hash run or a run without early chains.
+extern "C" int bsg_engine_tiers_debug(bsg_engine* e, uint64_t out[6]) {
+  if (!e || !out || e->enqueued) return BSG_EINVAL;
+  out[0] = e->last.nlong_grp;
+  out[1] = e->last.tickets_grp;
+  out[2] = e->last.helped;
+  out[3] = e->last.ntickets;
+  out[4] = out[5] = 0;
+  if (e->hash_mode || !e->ctr.p || e->ctr.cap < sizeof(Counters) + sizeof(Early)) return BSG_OK;
+  if (e->setdev()) return BSG_EDEVICE;
+  Early ea;
+  if (hipStreamSynchronize(e->stream) != hipSuccess) return BSG_EDEVICE;
+  if (hipMemcpy(&ea, e->dearly(), sizeof(Early), hipMemcpyDeviceToHost) != hipSuccess)
+    return BSG_EDEVICE;
+  for (int k = 0; k < kEarly; ++k) out[4 + k] = (ea.top[k] && ea.idx[k]) ? 1 : 0;
+  return BSG_OK;
+}
+
 int bsg_engine_timeline(const bsg_engine* e, uint64_t out[4]) {
   if (!e || !out) return BSG_EINVAL;
   out[0] = e->last.sha_start_rt;

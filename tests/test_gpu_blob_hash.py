@@ -109,16 +109,22 @@ def test_hasher_large_blob_small_path_pins_nothing_big(gpu):
         h.free()
 
 
-@pytest.mark.parametrize("long_kib", [15, 16, 50, 900])
-def test_hasher_small_batch_with_a_long_blob(gpu, long_kib):
+@pytest.mark.parametrize("long_kib,ntiny", [(15, 0), (16, 0), (50, 0), (900, 0), (16, 5000),
+                                            (20, 3000)],
+                         ids=["15", "16", "50", "900", "16-tiny5000", "20-tiny3000"])
+def test_hasher_small_batch_with_a_long_blob(gpu, long_kib, ntiny):
     """Round 6: a batch under the engine's byte threshold that holds a blob of 16 KiB or more
     (a split::Writer's tree nodes: geometric leaf counts) goes to the engine's wave-mode chains
     instead of one blob per lane; at 15 KiB it stays on the per-lane path. Both forms, through
-    bsg_hasher_sum and _sum_ptrs, against hashlib; the hasher pins only the batch's size."""
-    rng = np.random.default_rng(long_kib)
+    bsg_hasher_sum and _sum_ptrs, against hashlib; the hasher pins only the batch's size.
+    With ntiny more blobs of 0 to 200 bytes (every blob of such a batch takes a
+    wave ticket) the batch, still under 4 MiB, takes hundreds of group tickets."""
+    rng = np.random.default_rng(long_kib + ntiny)
     blobs = [rng.bytes(int(n)) for n in rng.integers(0, 12_000, 62)]
+    blobs += [rng.bytes(int(n)) for n in rng.integers(0, 201, ntiny)]
     blobs.insert(17, rng.bytes(long_kib << 10))
     blobs.insert(3, b"")
+    assert sum(map(len, blobs)) < 4 << 20
     want = [hashlib.sha256(b).digest() for b in blobs]
     h = gpu.Hasher()
     try:
@@ -169,13 +175,16 @@ def test_engine_hash_device_resident(gpu):
 
 @pytest.fixture(scope="module")
 def fill_boundary_blobs():
-    """Blobs whose block count nblocks = (L + 8) // 64 + 1 lands on and just past every ring-fill
-    size of k_sha: 1 | 2 (the padding spilling into a block of its own), 2 | 3 (a pair ticket's
-    fill), 8 | 9 (a group ticket's), 64 | 65 and 128 | 129 (a solo ticket's fill and a helped
-    chain's half, once and twice). With every job on wave tickets the 16 longest run solo
-    (8184 x 6, 8183 x 6, 4088 x 4) and the rest eight to a group ticket (4087 x 4 and all the
-    shorter ones: 34 jobs on 5 tickets, the last with 6 empty slots). 50 blobs, about 140 KiB;
-    expected refs from hashlib."""
+    """Blobs whose block count nblocks = (L + 8) // 64 + 1 lands on and just past the ring-fill
+    sizes of k_sha's solo and group tickets: 1 | 2 (the padding spilling into a block of its
+    own), 8 | 9 (a group ticket's fill), 64 | 65 and 128 | 129 (a solo ticket's, once and twice).
+    With every job on wave tickets (long_mode 2) the 16 longest run solo (8184 x 6, 8183 x 6,
+    4088 x 4) and the rest eight to a group ticket (4087 x 4 and all the shorter ones: 34 jobs
+    on 5 tickets, the last with 6 empty slots). That mode makes no pair tickets and no helped
+    chains (both need long_mode 0), and with long_mode 0 or 1 all 50 blobs, under the 64 KiB
+    wave-mode floor, go one per lane: the pair and helped paths have these edges in
+    tier_boundary_blobs below and in test_gpu_sha_tiers.py. 50 blobs, about 140 KiB; expected
+    refs from hashlib."""
     lens = [8184] * 6 + [8183] * 6 + [4088] * 4 + [4087] * 4
     lens += [0, 55, 56, 63, 64, 119, 120, 503, 504] * 3 + [1, 65, 127]
     assert len(lens) == 50 and all((n + 8) // 64 + 1 <= 129 for n in lens)
@@ -218,6 +227,52 @@ def test_engine_hash_fill_boundaries(gpu, fill_boundary_blobs, long_mode):
             assert (d["nlong"], d["wave_tickets"]) == (len(blobs), 16 + 5), d
         else:
             assert (d["nlong"], d["wave_tickets"]) == (0, 0), d
+    finally:
+        eng.close()
+        buf.free()
+
+
+@pytest.fixture(scope="module")
+def tier_boundary_blobs():
+    """One blob per length of sha_edges.tier_lengths(), shuffled: block counts on and next to
+    the fills of a helped solo chain (64, in two halves), a group ticket (8) and a pair ticket
+    (2), each with L % 64 in {55, 56, 63, 0, 1}, laid out so that the engine's own choice puts
+    the 16 longest on helped solo chains, 21 on group tickets, 41 on pair tickets and 15 on
+    single lanes. 93 blobs, 8.7 MB; expected refs from hashlib."""
+    import sha_edges
+    planned = sha_edges.tier_lengths()
+    lens = [n for v in planned.values() for n in v]
+    rng = np.random.default_rng(65)
+    rng.shuffle(lens)
+    blobs = [rng.bytes(int(n)) for n in lens]
+    return blobs, [hashlib.sha256(b).digest() for b in blobs], planned
+
+
+def test_engine_hash_tier_boundaries(gpu, tier_boundary_blobs):
+    """bsg_engine_hash on device-resident blobs (16-byte aligned) in the engine's auto mode:
+    helped solo chains, group tickets, pair tickets and single lanes in one launch, as the
+    counters show; every ref equals hashlib's."""
+    import sha_edges
+    blobs, want, planned = tier_boundary_blobs
+    off, o = [], 0
+    for b in blobs:
+        off.append(o)
+        o = (o + len(b) + 15) & ~15
+    host = np.zeros(o + gpu.READ_SLACK, dtype=np.uint8)
+    for b, x in zip(blobs, off):
+        host[x:x + len(b)] = np.frombuffer(b, dtype=np.uint8)
+    buf = gpu.DeviceBuffer(host.size)
+    eng = gpu.Engine()
+    try:
+        buf.from_host(host)
+        eng.hash(buf.ptr, off, [len(b) for b in blobs])
+        assert eng.finish() == len(blobs)
+        ch = eng.chunks()
+        got = [bytes(r) for r in ch["ref"]]
+        bad = [(len(b), (len(b) + 8) // 64 + 1) for b, g, w in zip(blobs, got, want) if g != w]
+        assert not bad, bad
+        assert list(ch["len"]) == [len(b) for b in blobs]
+        sha_edges.check_tiers(eng.diag(), eng.tiers(), planned, len(blobs))
     finally:
         eng.close()
         buf.free()
