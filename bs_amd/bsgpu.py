@@ -73,6 +73,13 @@ CHUNK_DTYPE = np.dtype(
 )
 assert CHUNK_DTYPE.itemsize == 56
 
+# bsg_tree_node: one split.Node blob of a stream's tree (Engine.trees)
+TREE_NODE_DTYPE = np.dtype(
+    [("blob_off", "<u8"), ("blob_len", "<u4"), ("stream", "<u4"), ("height", "<u4"),
+     ("reserved", "<u4"), ("ref", "u1", (32,))]
+)
+assert TREE_NODE_DTYPE.itemsize == 56
+
 _lib = None
 
 
@@ -127,6 +134,14 @@ def lib() -> ctypes.CDLL:
         "bsg_engine_copy_chunks": (ctypes.c_int, [vp, vp, ctypes.c_uint64]),
         "bsg_engine_copy_counts": (ctypes.c_int, [vp, u64p, ctypes.c_uint32]),
         "bsg_engine_stream": (vp, [vp]),
+        "bsg_engine_trees": (ctypes.c_int, [vp, u64p, u64p]),
+        "bsg_engine_copy_roots": (ctypes.c_int, [vp, vp, u64p, ctypes.c_uint32]),
+        "bsg_engine_copy_tree_nodes": (ctypes.c_int, [vp, vp, ctypes.c_uint64, vp,
+                                                      ctypes.c_uint64]),
+        "bsg_engine_tree_nodes_device": (vp, [vp]),
+        "bsg_engine_tree_arena_device": (vp, [vp]),
+        "bsg_engine_roots_device": (vp, [vp]),
+        "bsg_engine_trees_ms_debug": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_float)]),
         "bsg_engine_candidates": (ctypes.c_uint64, [vp]),
         "bsg_engine_profile": (ctypes.c_int, [vp, ctypes.c_int]),
         "bsg_engine_diag": (ctypes.c_int, [vp, u64p]),
@@ -417,9 +432,10 @@ class Engine:
             raise BsgError(err.value, "bsg_engine_create")
         self.nstreams = 0
 
-    def run(self, d_ptr: int, off, lens, bits: int = 16, min_size: int = 1024) -> None:
+    def run(self, d_ptr: int, off, lens, bits: int = 16, min_size: int = 1024,
+            fanout: int = 8) -> None:
         self._off, self._len = _u64(off), _u64(lens)
-        self._p = params(bits, min_size)
+        self._p = params(bits, min_size, fanout)
         self.nstreams = len(self._off)
         _check(lib().bsg_engine_run(self.h, d_ptr, _p(self._off, ctypes.c_uint64),
                                     _p(self._len, ctypes.c_uint64), self.nstreams,
@@ -450,6 +466,33 @@ class Engine:
         _check(lib().bsg_engine_copy_counts(self.h, _p(c, ctypes.c_uint64), self.nstreams),
                "bsg_engine_copy_counts")
         return c[: self.nstreams]
+
+    def trees(self):
+        """bsg_engine_trees: split.Writer's tree per stream of the last finished run, built on
+        the device. Returns (roots[ns, 32], node_counts[ns], nodes[TREE_NODE_DTYPE], arena[u8]):
+        node i's blob is arena[blob_off : blob_off + blob_len], a stream's last node its Root."""
+        nn, nb = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        _check(lib().bsg_engine_trees(self.h, ctypes.byref(nn), ctypes.byref(nb)),
+               "bsg_engine_trees")
+        roots = np.zeros((max(self.nstreams, 1), 32), dtype=np.uint8)
+        counts = np.zeros(max(self.nstreams, 1), dtype=np.uint64)
+        _check(lib().bsg_engine_copy_roots(self.h, roots.ctypes.data,
+                                           _p(counts, ctypes.c_uint64), self.nstreams),
+               "bsg_engine_copy_roots")
+        nodes = np.zeros(max(nn.value, 1), dtype=TREE_NODE_DTYPE)
+        arena = np.zeros(max(nb.value, 1), dtype=np.uint8)
+        _check(lib().bsg_engine_copy_tree_nodes(self.h, nodes.ctypes.data, nn.value,
+                                                arena.ctypes.data, nb.value),
+               "bsg_engine_copy_tree_nodes")
+        return (roots[: self.nstreams], counts[: self.nstreams], nodes[: nn.value],
+                arena[: nb.value])
+
+    def trees_ms(self) -> dict:
+        """The last trees() call's passes in ms (test tooling; needs profile() on)."""
+        out = (ctypes.c_float * 4)()
+        _check(lib().bsg_engine_trees_ms_debug(self.h, out), "bsg_engine_trees_ms_debug")
+        return {"layout": float(out[0]), "emit": float(out[1]), "hash": float(out[2]),
+                "total": float(out[3])}
 
     @property
     def stream(self) -> int:

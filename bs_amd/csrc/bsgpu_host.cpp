@@ -410,6 +410,24 @@ struct RunPlan {
   bool light = false;      // ... in the lightly loaded arrangement (bsg_engine, "Round 5")
 };
 
+// The sizes of one bsg_engine_trees call: the run's own (known when it finished), then the node
+// count and height bound from the counting pass, then the arena size from the layout passes.
+struct TreePlan {
+  uint32_t ns = 0;       // streams of the run
+  uint64_t M = 0;        // its records
+  uint32_t fanout = 8;
+  uint64_t nn = 0;       // listed nodes of all streams
+  uint32_t H = 1;        // heights of the tallest tree
+  uint64_t arena = 0;    // blob bytes (16-byte aligned blobs), without the read slack
+};
+// one hash run takes at most this many of a height's blobs (bsg_engine_hash's own bound)
+constexpr uint32_t kTreeHashBatch = 65535;
+// A height with at most this many nodes puts every node on a wave ticket (as bsg_hasher's small
+// batches do): the call waits for each height's longest node, and a typical node (10-60 KB) is
+// under kLongMinBlocks, where the engine's own choice would hash it per lane, ~4x slower per
+// block. More nodes than this keep every wave busy per lane, and the engine's choice stands.
+constexpr uint64_t kTreeWaveNodes = 4096;
+
 // Counters::error after a run
 int device_error(uint64_t code) {
   std::fprintf(stderr, "bsgpu: device sanity check failed (code %llu)\n", (unsigned long long)code);
@@ -457,6 +475,21 @@ struct bsg_engine {
   bool early_ok() const {
     return !snapshot && !hash_mode && knob(BSG_KNOB_EARLY) != 0;
   }
+
+  // bsg_engine_trees: split.Writer's tree per stream of the last finished split run. The tree
+  // work owns every buffer here; its node blobs are hashed by `hasher`, a second engine in hash
+  // mode on this engine's stream (it shares nothing with the run's buffers, so the records stay).
+  uint32_t fanout = 8;        // the last bsg_engine_run's
+  bool run_done = false;      // the last enqueue was a bsg_engine_run that finish() completed
+  bool borrowed_stream = false;  // `stream` belongs to the engine this one hashes nodes for
+  bsg_engine* hasher = nullptr;
+  DevBuf t_hdr, t_cstart, t_rmax, t_kcnt, t_tmp, t_close, t_shbase, t_meta, t_pc, t_pn, t_aoff,
+      t_part, t_descs, t_arena, t_nodes, t_roots, t_ncount;
+  PinBuf h_thdr;
+  TreePlan tree;              // the last bsg_engine_trees result's sizes
+  bool tree_valid = false;
+  std::vector<hipEvent_t> tev;  // profile: start, layout done, per height emit / hash done, end
+  float tree_ms[4] = {0, 0, 0, 0};  // profile: counting + layout, emit, hash, whole call
 
   // Round 5: a lightly loaded run (at most BSG_KNOB_LIGHT_BYTES, default 4 GiB, where the
   // longest chunk's chain is the step: configs[1], [3], [4]) keeps its early chains on the
@@ -794,6 +827,7 @@ struct bsg_engine {
 
   int enqueue() {
     int rc;
+    run_done = false;
     if (early_open) {  // a failed run left second-stream work its engine stream never waited for
       HCHECK(hipStreamSynchronize(estream));
       early_open = false;
@@ -819,6 +853,7 @@ struct bsg_engine {
   // (No candidates, so such a run cannot overflow: finish() never re-runs it.)
   int enqueue_hash() {
     int rc;
+    run_done = false;
     const RunPlan pl = plan_hash();
     if ((rc = reserve(pl)) || (rc = run_start(pl, stream))) return rc;
     mark(0);
@@ -857,6 +892,193 @@ struct bsg_engine {
         }
     }
     if (nchunks) *nchunks = last.nchunks;
+    run_done = !hash_mode && !snapshot;
+    return BSG_OK;
+  }
+
+  // A hash run whose descriptors a kernel wrote (d_src, device memory) instead of the host:
+  // blob i = data[desc[i].data_off .. + desc[i].len), record i = its ref. Enqueued on `stream`;
+  // the caller reads out / ctr on the same stream.
+  int enqueue_hash_device(const uint8_t* data, uint64_t span, const StreamDesc* d_src,
+                          uint32_t n, int sha_mode) {
+    int rc;
+    RunPlan pl;
+    pl.ns = n;
+    pl.data_span = std::max<uint64_t>(1, span);
+    pl.chunk_cap = n;
+    pl.jobs = 2ull * n;
+    if ((rc = reserve(pl))) return rc;
+    d_data = data;
+    nstreams = n;
+    hash_mode = true;
+    normalize(nullptr, &p, nullptr);
+    StartArgs st = start_args(pl);
+    st.src = d_src;
+    HCHECK(dbg("launch_start", stream, launch_start(st, stream)));
+    HCHECK(dbg("launch_blob_jobs", stream,
+               launch_blob_jobs(chunk_args(pl), streams.as<StreamDesc>(), pl.ns, stream, num_cus)));
+    const ShaArgs sh = sha_args(pl, sha_mode, nullptr);
+    return run_sha(pl, sh, stream);
+  }
+
+  TreeArgs tree_args(const TreePlan& tp) const {
+    TreeArgs a{};
+    a.rec = out.as<ChunkRec>();
+    a.M = tp.M;
+    a.scount = scount.as<uint64_t>();
+    a.ns = tp.ns;
+    a.fanout = tp.fanout;
+    a.H = tp.H;
+    a.nn = tp.nn;
+    a.arena_bytes = tp.arena;
+    a.hdr = t_hdr.as<TreeHdr>();
+    a.cstart = t_cstart.as<uint64_t>();
+    a.rmax = t_rmax.as<uint32_t>();
+    a.kcnt = t_kcnt.as<uint8_t>();
+    a.tmp = t_tmp.as<uint64_t>();
+    a.close = t_close.as<uint64_t>();
+    a.shbase = t_shbase.as<uint64_t>();
+    a.meta = t_meta.as<TreeNodeMeta>();
+    a.pc = t_pc.as<uint64_t>();
+    a.pn = t_pn.as<uint64_t>();
+    a.aoff = t_aoff.as<uint64_t>();
+    a.part = t_part.as<uint64_t>();
+    a.arena = t_arena.as<uint8_t>();
+    a.nodes = t_nodes.as<TreeNode>();
+    a.roots = t_roots.as<uint8_t>();
+    a.ncount = t_ncount.as<uint64_t>();
+    return a;
+  }
+
+  // the header to the host; BSG_EDEVICE if a device-side check failed
+  int tree_readback(TreeHdr* h) {
+    HCHECK(hipMemcpyAsync(h_thdr.p, t_hdr.p, sizeof(TreeHdr), hipMemcpyDeviceToHost, stream));
+    HCHECK(stream_wait(stream));
+    *h = *h_thdr.as<TreeHdr>();
+    if (h->error) {
+      std::fprintf(stderr, "bsgpu: tree sanity check failed (code %llu)\n",
+                   (unsigned long long)h->error);
+      return BSG_EDEVICE;
+    }
+    return BSG_OK;
+  }
+
+  hipEvent_t tree_event(size_t i) {
+    while (tev.size() <= i) {
+      hipEvent_t e = nullptr;
+      if (hipEventCreate(&e) != hipSuccess) (void)hipGetLastError();
+      tev.push_back(e);
+    }
+    if (tev[i]) (void)hipEventRecord(tev[i], stream);
+    return tev[i];
+  }
+
+  int trees() {
+    if (!run_done || snapshot || hash_mode) return BSG_ESTATE;
+    int rc;
+    tree_valid = false;
+    TreePlan tp;
+    tp.ns = nstreams;
+    tp.M = last.nchunks;
+    tp.fanout = fanout ? fanout : 8;
+    const uint64_t nn1 = tp.ns ? tp.ns : 1, m1 = tp.M ? tp.M : 1;
+    const bool prof = profile != 0;
+    size_t nev = 0;
+
+    // counting: chunk ranges, Root heights, node total
+    HCHECK(t_hdr.ensure(sizeof(TreeHdr)));
+    HCHECK(h_thdr.ensure(sizeof(TreeHdr)));
+    HCHECK(t_cstart.ensure(8 * (nn1 + 1)));
+    HCHECK(t_rmax.ensure(4 * nn1));
+    HCHECK(t_kcnt.ensure(m1));
+    HCHECK(t_tmp.ensure(8 * (m1 + 1)));
+    HCHECK(t_pc.ensure(8 * (m1 + 1)));
+    HCHECK(t_part.ensure(8 * tree_scan_parts(std::max<uint64_t>(m1, nn1))));
+    HCHECK(t_roots.ensure(32 * nn1));
+    HCHECK(t_ncount.ensure(8 * nn1));
+    if (prof) tree_event(nev++);
+    HCHECK(hipMemsetAsync(t_hdr.p, 0, sizeof(TreeHdr), stream));
+    HCHECK(hipMemsetAsync(t_rmax.p, 0, 4 * nn1, stream));
+    HCHECK(dbg("launch_tree_count", stream, launch_tree_count(tree_args(tp), stream, num_cus)));
+    TreeHdr h;
+    if ((rc = tree_readback(&h))) return rc;
+    tp.nn = h.nnodes;
+    tp.H = (uint32_t)h.max_r + 1;
+    if (tp.H > kTreeMaxHeights) return BSG_EDEVICE;
+
+    if (tp.nn) {
+      // layout: every node's children, listed place, blob length and arena offset
+      HCHECK(t_close.ensure(8 * tp.nn));
+      HCHECK(t_shbase.ensure(8 * ((uint64_t)tp.ns * tp.H + 1)));
+      HCHECK(t_meta.ensure(sizeof(TreeNodeMeta) * tp.nn));
+      HCHECK(t_pn.ensure(8 * (tp.nn + 1)));
+      HCHECK(t_aoff.ensure(8 * (tp.nn + 1)));
+      HCHECK(t_nodes.ensure(sizeof(TreeNode) * tp.nn));
+      HCHECK(t_part.ensure(8 * tree_scan_parts(std::max<uint64_t>(
+                                   std::max<uint64_t>(m1, tp.nn), (uint64_t)tp.ns * tp.H))));
+      HCHECK(dbg("launch_tree_layout", stream, launch_tree_layout(tree_args(tp), stream, num_cus)));
+      if ((rc = tree_readback(&h))) return rc;
+      if (h.hoff[tp.H] != tp.nn) return BSG_EDEVICE;
+      tp.arena = h.arena_bytes;
+      HCHECK(t_arena.ensure(tp.arena + kReadSlack));
+      HCHECK(hipMemsetAsync(t_arena.p, 0, tp.arena + kReadSlack, stream));
+      if (prof) tree_event(nev++);
+
+      if (!hasher) {
+        hasher = new (std::nothrow) bsg_engine();
+        if (!hasher) return BSG_ENOMEM;
+        hasher->dev = dev;
+        hasher->num_cus = num_cus;
+        hasher->stream = stream;
+        hasher->borrowed_stream = true;
+      }
+      // height by height: emit the blobs, hash them, refs into the listed records (where the
+      // next height's emit reads them)
+      TreeArgs ta = tree_args(tp);
+      for (ta.h = 0; ta.h < tp.H; ++ta.h) {
+        const uint64_t u0 = h.hoff[ta.h], n = h.hoff[ta.h + 1] - u0;
+        const uint64_t children = ta.h ? u0 - h.hoff[ta.h - 1] : tp.M;
+        HCHECK(dbg("launch_tree_emit", stream, launch_tree_emit(ta, children, stream, num_cus)));
+        if (prof) tree_event(nev++);
+        for (uint64_t b = 0; b < n; b += kTreeHashBatch) {
+          const uint32_t nb = (uint32_t)std::min<uint64_t>(kTreeHashBatch, n - b);
+          HCHECK(t_descs.ensure(sizeof(StreamDesc) * nb));
+          HCHECK(launch_tree_descs(ta, u0 + b, nb, t_descs.as<StreamDesc>(), stream, num_cus));
+          if ((rc = hasher->enqueue_hash_device(t_arena.as<uint8_t>(), tp.arena,
+                                                t_descs.as<StreamDesc>(), nb,
+                                                n <= kTreeWaveNodes ? 2 : long_mode())))
+            return rc;
+          HCHECK(launch_tree_refs(ta, u0 + b, nb, hasher->out.as<ChunkRec>(), hasher->dctr(),
+                                  stream, num_cus));
+        }
+        if (prof) tree_event(nev++);
+      }
+    }
+    HCHECK(dbg("launch_tree_roots", stream, launch_tree_roots(tree_args(tp), stream, num_cus)));
+    if (prof) tree_event(nev++);
+    if ((rc = tree_readback(&h))) return rc;
+    if (prof) {
+      auto ms = [&](size_t i, size_t j) {
+        float v = 0.f;
+        if (i >= nev || j >= nev || !tev[i] || !tev[j] ||
+            hipEventElapsedTime(&v, tev[i], tev[j]) != hipSuccess) {
+          (void)hipGetLastError();
+          return 0.f;
+        }
+        return v;
+      };
+      tree_ms[0] = tree_ms[1] = tree_ms[2] = 0.f;
+      if (tp.nn) {
+        tree_ms[0] = ms(0, 1);
+        for (uint32_t k = 0; k < tp.H; ++k) {
+          tree_ms[1] += ms(1 + 2 * k, 2 + 2 * k);
+          tree_ms[2] += ms(2 + 2 * k, 3 + 2 * k);
+        }
+      }
+      tree_ms[3] = ms(0, nev - 1);
+    }
+    tree = tp;
+    tree_valid = true;
     return BSG_OK;
   }
 };
@@ -1985,6 +2207,17 @@ void bsg_engine_destroy(bsg_engine* e) {
   if (!e) return;
   hipSetDevice(e->dev);
   if (e->stream) hipStreamSynchronize(e->stream);
+  if (e->hasher) {  // (it ran on e->stream, synchronised above)
+    bsg_engine_destroy(e->hasher);
+    e->hasher = nullptr;
+  }
+  DevBuf* tbufs[] = {&e->t_hdr, &e->t_cstart, &e->t_rmax, &e->t_kcnt, &e->t_tmp, &e->t_close,
+                     &e->t_shbase, &e->t_meta, &e->t_pc, &e->t_pn, &e->t_aoff, &e->t_part,
+                     &e->t_descs, &e->t_arena, &e->t_nodes, &e->t_roots, &e->t_ncount};
+  for (DevBuf* b : tbufs) b->release();
+  e->h_thdr.release();
+  for (hipEvent_t ev : e->tev)
+    if (ev) hipEventDestroy(ev);
   // a failed run may have left early chains (k_pick / k_early on estream) that the engine
   // stream never waited for: they read cand, ctr and the data, so they end before any release
   if (e->estream) hipStreamSynchronize(e->estream);
@@ -2005,7 +2238,7 @@ void bsg_engine_destroy(bsg_engine* e) {
   if (e->pick_ev) hipEventDestroy(e->pick_ev);
   if (e->early_ev) hipEventDestroy(e->early_ev);
   if (e->estream) stream_release(e->dev, e->estream);  // (synchronised above)
-  if (e->stream) stream_release(e->dev, e->stream);
+  if (e->stream && !e->borrowed_stream) stream_release(e->dev, e->stream);
   delete e;
 }
 
@@ -2056,16 +2289,20 @@ static int engine_batch(bsg_engine* e, const uint8_t* d_data, const uint64_t* of
 int bsg_engine_run(bsg_engine* e, const uint8_t* d_data, const uint64_t* off, const uint64_t* len,
                    uint32_t nstreams, const bsg_params* params) {
   Params p;
-  int rc = normalize(params, &p, nullptr);
+  bsg_params norm;
+  int rc = normalize(params, &p, &norm);
   if (rc) return rc;
+  if (e) e->run_done = false;
   if ((rc = engine_batch(e, d_data, off, len, nstreams))) return rc;
   e->p = p;
+  e->fanout = norm.fanout;
   e->hash_mode = false;
   return e->enqueue();
 }
 
 int bsg_engine_hash(bsg_engine* e, const uint8_t* d_data, const uint64_t* off, const uint64_t* len,
                     uint32_t nblobs) {
+  if (e) e->run_done = false;
   int rc = engine_batch(e, d_data, off, len, nblobs);
   if (rc) return rc;
   normalize(nullptr, &e->p, nullptr);
@@ -2103,6 +2340,57 @@ int bsg_engine_copy_counts(bsg_engine* e, uint64_t* counts, uint32_t nstreams) {
 }
 
 void* bsg_engine_stream(bsg_engine* e) { return e ? (void*)e->stream : nullptr; }
+
+int bsg_engine_trees(bsg_engine* e, uint64_t* nnodes, uint64_t* arena_bytes) {
+  if (!e || !nnodes || !arena_bytes) return BSG_EINVAL;
+  int rc = e->setdev();
+  if (rc) return rc;
+  if ((rc = e->trees())) return rc;
+  *nnodes = e->tree.nn;
+  *arena_bytes = e->tree.arena;
+  return BSG_OK;
+}
+
+int bsg_engine_copy_roots(bsg_engine* e, uint8_t* roots, uint64_t* node_counts,
+                          uint32_t nstreams) {
+  if (!e || !roots) return BSG_EINVAL;
+  if (!e->tree_valid || !e->run_done) return BSG_ESTATE;
+  if (nstreams > e->tree.ns) return BSG_EINVAL;
+  int rc = e->setdev();
+  if (rc) return rc;
+  if (nstreams) {
+    HCHECK(hipMemcpy(roots, e->t_roots.p, 32ull * nstreams, hipMemcpyDeviceToHost));
+    if (node_counts)
+      HCHECK(hipMemcpy(node_counts, e->t_ncount.p, 8ull * nstreams, hipMemcpyDeviceToHost));
+  }
+  return BSG_OK;
+}
+
+int bsg_engine_copy_tree_nodes(bsg_engine* e, bsg_tree_node* out, uint64_t cap, uint8_t* arena,
+                               uint64_t arena_cap) {
+  if (!e || (!out && cap) || (!arena && arena_cap)) return BSG_EINVAL;
+  if (!e->tree_valid || !e->run_done) return BSG_ESTATE;
+  int rc = e->setdev();
+  if (rc) return rc;
+  const uint64_t n = std::min<uint64_t>(cap, e->tree.nn);
+  const uint64_t nb = std::min<uint64_t>(arena_cap, e->tree.arena);
+  if (n) HCHECK(hipMemcpy(out, e->t_nodes.p, sizeof(bsg_tree_node) * n, hipMemcpyDeviceToHost));
+  if (nb) HCHECK(hipMemcpy(arena, e->t_arena.p, nb, hipMemcpyDeviceToHost));
+  return BSG_OK;
+}
+
+const bsg_tree_node* bsg_engine_tree_nodes_device(const bsg_engine* e) {
+  return e && e->tree_valid && e->run_done ? static_cast<const bsg_tree_node*>(e->t_nodes.p)
+                                           : nullptr;
+}
+
+const uint8_t* bsg_engine_tree_arena_device(const bsg_engine* e) {
+  return e && e->tree_valid && e->run_done ? e->t_arena.as<uint8_t>() : nullptr;
+}
+
+const uint8_t* bsg_engine_roots_device(const bsg_engine* e) {
+  return e && e->tree_valid && e->run_done ? e->t_roots.as<uint8_t>() : nullptr;
+}
 
 int bsg_engine_profile(bsg_engine* e, int enable) {
   if (!e || enable < 0 || enable > 2) return BSG_EINVAL;
@@ -2164,6 +2452,16 @@ extern "C" int bsg_engine_tiers_debug(bsg_engine* e, uint64_t out[6]) {
   if (hipMemcpy(&ea, e->dearly(), sizeof(Early), hipMemcpyDeviceToHost) != hipSuccess)
     return BSG_EDEVICE;
   for (int k = 0; k < kEarly; ++k) out[4 + k] = (ea.top[k] && ea.idx[k]) ? 1 : 0;
+  return BSG_OK;
+}
+
+// Test and measurement tooling (not in bsgpu.h): the last bsg_engine_trees call's passes in ms,
+// timed with HIP events on the engine stream when bsg_engine_profile is on: [0] counting and
+// layout, [1] emit, [2] node hashes, [3] the whole call.
+extern "C" int bsg_engine_trees_ms_debug(const bsg_engine* e, float out[4]) {
+  if (!e || !out) return BSG_EINVAL;
+  if (!e->profile || !e->tree_valid) return BSG_ESTATE;
+  for (int i = 0; i < 4; ++i) out[i] = e->tree_ms[i];
   return BSG_OK;
 }
 

@@ -177,4 +177,33 @@ constexpr int kRingWords = 65 * kLongRow;  // per wave: 64 K+W rows + one row of
 constexpr int kLptBuckets = 4096;          // longest-first job order: counting sort on nblocks
 constexpr uint64_t kReadSlack = 256;       // readable bytes required after every stream's data
 
+// split.Writer's tree built on the device (bsg_engine_trees; bsgpu_tree.inc). Levels are at most
+// 32 (TrailingZeros32 - Bits) and fanout at least 1, so a tree has at most 33 heights.
+constexpr uint32_t kTreeMaxHeights = 40;
+struct TreeNode {              // == bsg_tree_node (include/bsgpu.h)
+  uint64_t blob_off;
+  uint32_t blob_len;
+  uint32_t stream;
+  uint32_t height;
+  uint32_t reserved;
+  uint8_t ref[32];
+};
+static_assert(sizeof(TreeNode) == 56, "TreeNode layout");
+struct TreeHdr {               // totals of one bsg_engine_trees call, read back by the host
+  uint64_t nnodes;             // listed nodes of all streams
+  uint64_t arena_bytes;        // blob bytes, every blob 16-byte aligned
+  uint64_t max_r;              // the largest Root height
+  uint64_t error;              // a consistency check failed (bug guard; the result is invalid)
+  uint64_t hoff[kTreeMaxHeights + 1];  // height h's nodes have internal ids [hoff[h], hoff[h+1])
+};
+struct TreeNodeMeta {          // per internal id (height-major, then stream, then offset)
+  uint64_t child0;             // first child: a chunk index (height 0) or an internal id
+  uint64_t nchild;
+  uint64_t offset, size;       // Node.offset / Node.size
+  uint64_t out_idx;            // its place in the listed order
+  uint64_t blob_off;
+  uint32_t blob_len;
+  uint32_t stream;
+};
+
 }  // namespace bsg

@@ -2610,4 +2610,6 @@ hipError_t launch_sha_blobs(const BlobShaArgs& a, hipStream_t s, int num_cus) {
   return hipGetLastError();
 }
 
+#include "bsgpu_tree.inc"
+
 }  // namespace bsg

@@ -159,4 +159,43 @@ hipError_t launch_copy_out(const void* src, void* dst, uint64_t bytes, hipStream
 hipError_t launch_fill_splitmix(uint8_t* p, uint64_t n, uint64_t seed, hipStream_t s,
                                 int num_cus);
 
+// bsg_engine_trees (bsgpu_tree.inc): the records of a finished run in, the listed nodes, their
+// blobs and the Roots out. Every buffer but rec / scount belongs to the tree work.
+struct TreeArgs {
+  const ChunkRec* rec;      // [M] the run's records, stream-major
+  uint64_t M;
+  const uint64_t* scount;   // [ns] chunks per stream
+  uint32_t ns;
+  uint32_t fanout;
+  uint32_t H;               // heights of the tallest tree (after the first readback)
+  uint32_t h;               // the height a per-height pass works on
+  uint64_t nn;              // nodes of all streams (after the first readback)
+  uint64_t arena_bytes;     // (after the second readback)
+  TreeHdr* hdr;
+  uint64_t* cstart;         // [ns + 1] first chunk of each stream
+  uint32_t* rmax;           // [ns] Root height R, zeroed per call
+  uint8_t* kcnt;            // [M] nodes chunk i closes
+  uint64_t* tmp;            // [M + 1] a height's compaction ranks
+  uint64_t* close;          // [nn] closing chunk by internal id
+  uint64_t* shbase;         // [ns * H + 1] listed index of (stream, height)'s first node
+  TreeNodeMeta* meta;       // [nn]
+  uint64_t* pc;             // [M + 1] prefix of the leaf entries' bytes
+  uint64_t* pn;             // [nn + 1] prefix of the node entries' bytes
+  uint64_t* aoff;           // [nn + 1] arena offsets
+  uint64_t* part;           // [tree_scan_parts(n)] workgroup sums of a prefix pass
+  uint8_t* arena;
+  TreeNode* nodes;          // [nn] listed order
+  uint8_t* roots;           // [ns * 32]
+  uint64_t* ncount;         // [ns] listed nodes per stream
+};
+uint64_t tree_scan_parts(uint64_t n);
+hipError_t launch_tree_count(const TreeArgs& a, hipStream_t s, int num_cus);
+hipError_t launch_tree_layout(TreeArgs a, hipStream_t s, int num_cus);
+hipError_t launch_tree_emit(const TreeArgs& a, uint64_t children, hipStream_t s, int num_cus);
+hipError_t launch_tree_descs(const TreeArgs& a, uint64_t u0, uint32_t n, StreamDesc* d,
+                             hipStream_t s, int num_cus);
+hipError_t launch_tree_refs(const TreeArgs& a, uint64_t u0, uint32_t n, const ChunkRec* hashed,
+                            const Counters* hctr, hipStream_t s, int num_cus);
+hipError_t launch_tree_roots(const TreeArgs& a, hipStream_t s, int num_cus);
+
 }  // namespace bsg

@@ -53,7 +53,7 @@ extern "C" {
 typedef struct bsg_params {
   uint32_t split_bits; /* Bits(n): trailing zero bits for a boundary (0 = 13) */
   uint32_t min_size;   /* MinSize(n): minimum chunk size (0 = 64) */
-  uint32_t fanout;     /* Fanout(n): tree level divisor (host tree only; 0 = 8) */
+  uint32_t fanout;     /* Fanout(n): tree level divisor (Writer, bsg_engine_trees; 0 = 8) */
   uint32_t reserved;
 } bsg_params;
 
@@ -188,6 +188,42 @@ int bsg_engine_copy_chunks(bsg_engine* eng, bsg_chunk* out, uint64_t cap);
 int bsg_engine_copy_counts(bsg_engine* eng, uint64_t* counts, uint32_t nstreams);
 /* The engine's HIP stream (hipStream_t), e.g. for event timing. */
 void* bsg_engine_stream(bsg_engine* eng);
+/* ---- split.Writer's tree and Root per stream of a run, built on the device ---- */
+/* One split.Node blob of a stream's tree (split/split.proto:6-26), as PutProto would store it. */
+typedef struct bsg_tree_node {
+  uint64_t blob_off;   /* its serialized bytes: arena[blob_off .. blob_off + blob_len) */
+  uint32_t blob_len;
+  uint32_t stream;
+  uint32_t height;     /* 0: a node of leaves (chunks); h: its children are nodes of height h-1 */
+  uint32_t reserved;
+  uint8_t ref[32];     /* SHA-256 of the blob */
+} bsg_tree_node;       /* 56 bytes */
+/* Builds, on the device, split.Writer's tree for every stream of the last finished
+ * bsg_engine_run (fanout = that run's params.fanout, 0 = 8): TreeBuilder.Add(chunk, level/fanout)
+ * per record, TreeBuilder.Root's fold of every non-empty level, the single-child prune, and
+ * PutProto's ref of every node (split/split.go:51-126). Waits for completion. *nnodes /
+ * *arena_bytes: totals (blobs start 16-byte aligned in the arena, the gaps are zero).
+ * The node list holds exactly the blobs reachable from each stream's Root, the Root's own blob
+ * included, stream-major, then height ascending, then stream offset ascending: a stream's last
+ * node is its Root, and a caller that stores the nodes in list order with PutWithRef, after the
+ * chunks, never stores a node before what it points to (split/split.go:71-77). When the
+ * would-be root is pruned, split.Writer has also stored the single-child nodes it pruned
+ * through; nothing references them and they are NOT listed.
+ * BSG_EINVAL for null arguments; BSG_ESTATE unless the engine's last enqueue was a
+ * bsg_engine_run that bsg_engine_finish completed successfully (not: no run, a bsg_engine_hash
+ * run, an unfinished or failed run). Calling it twice on one run gives the same result. */
+int bsg_engine_trees(bsg_engine* eng, uint64_t* nnodes, uint64_t* arena_bytes);
+/* Root per stream (32 bytes each; all zero for an empty stream, bs.Zero) and, if node_counts is
+ * not NULL, the number of nodes per stream. */
+int bsg_engine_copy_roots(bsg_engine* eng, uint8_t* roots, uint64_t* node_counts, uint32_t nstreams);
+/* Node records (up to cap) and the blob arena (up to arena_cap bytes) to host memory. */
+int bsg_engine_copy_tree_nodes(bsg_engine* eng, bsg_tree_node* out, uint64_t cap,
+                               uint8_t* arena, uint64_t arena_cap);
+/* Device pointers, valid until the next run or the next bsg_engine_trees (NULL without a tree). */
+const bsg_tree_node* bsg_engine_tree_nodes_device(const bsg_engine* eng);
+const uint8_t* bsg_engine_tree_arena_device(const bsg_engine* eng);
+const uint8_t* bsg_engine_roots_device(const bsg_engine* eng);
+
 /* Per-stage HIP event timing of later runs, and the last finished run's stage durations in
  * ms: [0] rolling scan (k_scan), [1] prefix/compact/select/chunks, [2] SHA-256 (k_sha, and the
  * early chains' tail). Timed on the engine's own stream. enable: 0 off, 1 every stage (four
