@@ -147,6 +147,7 @@ def lib() -> ctypes.CDLL:
         "bsg_engine_diag": (ctypes.c_int, [vp, u64p]),
         "bsg_engine_timeline": (ctypes.c_int, [vp, u64p]),
         "bsg_engine_tiers_debug": (ctypes.c_int, [vp, u64p]),
+        "bsg_engine_rescan_debug": (ctypes.c_uint64, [vp]),
         "bsg_engine_stage_ms": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_float)]),
         "bsg_split_hash_batch": (ctypes.c_int, [ctypes.c_int, vp, u64p, u64p, ctypes.c_uint32,
                                                 ctypes.POINTER(Params), u32p, vp,
@@ -544,6 +545,12 @@ class Engine:
     @property
     def candidates(self) -> int:
         return lib().bsg_engine_candidates(self.h)
+
+    @property
+    def rescan_strips(self) -> int:
+        """bsg_engine_rescan_debug (test tooling, not in bsgpu.h): strips of the last finished
+        run with more candidates than slots, which k_rescan scanned again."""
+        return int(lib().bsg_engine_rescan_debug(self.h))
 
     def close(self) -> None:
         if self.h:

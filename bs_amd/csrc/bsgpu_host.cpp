@@ -2455,6 +2455,13 @@ extern "C" int bsg_engine_tiers_debug(bsg_engine* e, uint64_t out[6]) {
   return BSG_OK;
 }
 
+// Test tooling (not in include/bsgpu.h): Counters::rescan of the last finished run, the strips
+// whose candidates outnumbered their kSlotCap slots and went through k_rescan; ~0 while a run is
+// in flight or without an engine.
+extern "C" uint64_t bsg_engine_rescan_debug(const bsg_engine* e) {
+  return e && !e->enqueued ? e->last.rescan : ~0ull;
+}
+
 // Test and measurement tooling (not in bsgpu.h): the last bsg_engine_trees call's passes in ms,
 // timed with HIP events on the engine stream when bsg_engine_profile is on: [0] counting and
 // layout, [1] emit, [2] node hashes, [3] the whole call.

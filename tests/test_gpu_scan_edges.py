@@ -14,49 +14,9 @@ planted position is a candidate whatever precedes it; the test checks that the o
 import numpy as np
 import pytest
 
+from planting import STRIP, planted_stream
+
 pytestmark = pytest.mark.gpu
-
-STRIP = 2048
-
-
-def _rotl(x, r):
-    r %= 32
-    if r == 0:
-        return x
-    return ((x << np.uint32(r)) | (x >> np.uint32(32 - r))).astype(np.uint32)
-
-
-def zero_windows(table, count, low, seed):
-    """`count` 64-byte windows whose window hash has its `low` low bits zero: 62 random bytes,
-    then the two last bytes searched over all 65,536 pairs."""
-    T = np.asarray(table, dtype=np.uint32)
-    mask = np.uint32((1 << low) - 1)
-    rng = np.random.default_rng(seed)
-    a62 = _rotl(T, 1)          # byte 62 (one step before the newest): rotl 1
-    out = []
-    while len(out) < count:
-        pre = rng.integers(0, 256, 62, dtype=np.uint8)
-        h = np.uint32(0)
-        for i, b in enumerate(pre):
-            h ^= _rotl(np.array([T[b]], dtype=np.uint32), 63 - i)[0]
-        hh = (h ^ a62[:, None] ^ T[None, :]) & mask   # [b62, b63]
-        hit = np.argwhere(hh == 0)
-        if len(hit):
-            b62, b63 = hit[rng.integers(0, len(hit))]
-            out.append(np.concatenate([pre, np.array([b62, b63], dtype=np.uint8)]))
-    return out
-
-
-def planted_stream(table, n, low, seed):
-    """n random bytes with a zero window ending at offset (j mod 64) of every strip j >= 1 that
-    holds it; returns (bytes, planted end positions)."""
-    rng = np.random.default_rng(seed + 7)
-    data = rng.integers(0, 256, n, dtype=np.uint8)
-    ends = [STRIP * j + (j % 64) for j in range(1, n // STRIP + 1) if STRIP * j + (j % 64) < n]
-    wins = zero_windows(table, len(ends), low, seed)
-    for p, w in zip(ends, wins):
-        data[p - 63:p + 1] = w
-    return data, ends
 
 
 def _tuples(ch):
