@@ -148,6 +148,7 @@ def lib() -> ctypes.CDLL:
         "bsg_engine_timeline": (ctypes.c_int, [vp, u64p]),
         "bsg_engine_tiers_debug": (ctypes.c_int, [vp, u64p]),
         "bsg_engine_rescan_debug": (ctypes.c_uint64, [vp]),
+        "bsg_engine_regions_debug": (ctypes.c_int, [vp, vp, ctypes.c_uint64]),
         "bsg_engine_stage_ms": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_float)]),
         "bsg_split_hash_batch": (ctypes.c_int, [ctypes.c_int, vp, u64p, u64p, ctypes.c_uint32,
                                                 ctypes.POINTER(Params), u32p, vp,
@@ -309,6 +310,49 @@ def split_hash_batch(streams: list[bytes] | list[np.ndarray], bits: int = 16,
     return out[: n.value], counts[: len(arrs)]
 
 
+def _refs_list(refs: np.ndarray, n: int) -> list[bytes]:
+    return [refs[32 * i:32 * i + 32].tobytes() for i in range(n)]
+
+
+def _base_ptr(base) -> int:
+    """A base address: a host array's data pointer, or an int (a host or device address)."""
+    return int(base.ctypes.data) if isinstance(base, np.ndarray) else int(base)
+
+
+def split_hash_batch_at(base: np.ndarray, off, lens, bits: int = 16, min_size: int = 1024,
+                        table=None, device: int = 0):
+    """bsg_split_hash_batch over the caller's layout: stream i is base[off[i] : off[i] + lens[i]]
+    of one host array (any order, gaps, overlaps; no alignment). Returns (chunks, counts)."""
+    assert isinstance(base, np.ndarray) and base.dtype == np.uint8 and base.flags.c_contiguous
+    off, lens = _u64(off), _u64(lens)
+    assert len(off) == len(lens)
+    ns = len(off)
+    cap = int(sum(int(l) // (min_size or 64) + 2 for l in lens)) + 1
+    out = np.zeros(cap, dtype=CHUNK_DTYPE)
+    counts = np.zeros(max(ns, 1), dtype=np.uint64)
+    n = ctypes.c_uint64(0)
+    p = params(bits, min_size)
+    _t, tp = _table_arg(table)
+    rc = lib().bsg_split_hash_batch(device, base.ctypes.data, _p(off, ctypes.c_uint64),
+                                    _p(lens, ctypes.c_uint64), ns, ctypes.byref(p), tp,
+                                    out.ctypes.data, cap, _p(counts, ctypes.c_uint64),
+                                    ctypes.byref(n))
+    _check(rc, "bsg_split_hash_batch")
+    return out[: n.value], counts[:ns]
+
+
+def sha256_batch_at(base, off, lens, device: int = 0) -> list[bytes]:
+    """bsg_sha256_batch over the caller's layout: blob i is base[off[i] .. off[i] + lens[i]),
+    base a host uint8 array or an address (host or device memory)."""
+    off, lens = _u64(off), _u64(lens)
+    assert len(off) == len(lens)
+    refs = np.zeros(32 * max(len(off), 1), dtype=np.uint8)
+    rc = lib().bsg_sha256_batch(device, _base_ptr(base), _p(off, ctypes.c_uint64),
+                                _p(lens, ctypes.c_uint64), len(off), refs.ctypes.data)
+    _check(rc, "bsg_sha256_batch")
+    return _refs_list(refs, len(off))
+
+
 def sha256_batch(blobs: list[bytes], device: int = 0) -> list[bytes]:
     arrs = [np.frombuffer(bytes(b), dtype=np.uint8) for b in blobs]
     lens = _u64([len(a) for a in arrs])
@@ -353,6 +397,17 @@ class Hasher:
                                     _p(lens, ctypes.c_uint64), len(arrs), refs.ctypes.data),
                "bsg_hasher_sum")
         return [refs[32 * i:32 * i + 32].tobytes() for i in range(len(blobs))]
+
+    def sum_at(self, base, off, lens) -> list[bytes]:
+        """bsg_hasher_sum over the caller's layout: blob i is base[off[i] .. off[i] + lens[i]),
+        base a host uint8 array or an address (host or device memory)."""
+        off, lens = _u64(off), _u64(lens)
+        assert len(off) == len(lens)
+        refs = np.zeros(32 * max(len(off), 1), dtype=np.uint8)
+        _check(lib().bsg_hasher_sum(self.h, _base_ptr(base), _p(off, ctypes.c_uint64),
+                                    _p(lens, ctypes.c_uint64), len(off), refs.ctypes.data),
+               "bsg_hasher_sum")
+        return _refs_list(refs, len(off))
 
     def pinned_bytes(self) -> int:
         """bsg_hasher_pinned_bytes: pinned host memory the hasher holds (diagnostics)."""
@@ -541,6 +596,19 @@ class Engine:
                "bsg_engine_tiers_debug")
         return {"nlong_grp": int(d[0]), "tickets_grp": int(d[1]), "helped": int(d[2]),
                 "wave_tickets": int(d[3]), "early": (bool(d[4]), bool(d[5]))}
+
+    def regions(self) -> dict:
+        """bsg_engine_regions_debug (test tooling, not in bsgpu.h): the address regions of the
+        last finished run's per-lane SHA-256 jobs (Regions in bsgpu_internal.h). `nregions` = R
+        and `off[0..R]`: region r holds off[r + 1] - off[r] jobs."""
+        kmax = 256  # kMaxRegions; the record starts nregions, rr, pad[6], head[kmax], off[kmax+1]
+        d = np.zeros(8 + kmax + kmax + 1, dtype=np.uint64)
+        _check(lib().bsg_engine_regions_debug(self.h, d.ctypes.data, d.nbytes),
+               "bsg_engine_regions_debug")
+        R = int(d[0])
+        if not 1 <= R <= kmax:
+            raise BsgError(-5, f"bsg_engine_regions_debug: nregions {R}")
+        return {"nregions": R, "off": [int(x) for x in d[8 + kmax: 8 + kmax + R + 1]]}
 
     @property
     def candidates(self) -> int:

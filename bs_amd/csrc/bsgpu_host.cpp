@@ -2242,17 +2242,25 @@ void bsg_engine_destroy(bsg_engine* e) {
   delete e;
 }
 
-// Checks a device-resident batch (16-byte aligned offsets, streams under 2^40 bytes, the read
-// slack inside the allocation) and fills the engine's descriptors: fresh, final streams.
+// Checks a device-resident batch (a 16-byte aligned base and offsets, streams under 2^40 bytes
+// whose ends do not wrap, the read slack inside the allocation) and fills the engine's
+// descriptors: fresh, final streams. The streams may lie in any order, apart or on top of each
+// other. The argument checks come before the first HIP call: a wrapped off + len would pass the
+// allocation check below and hand the kernels a wild address.
 static int engine_batch(bsg_engine* e, const uint8_t* d_data, const uint64_t* off,
                         const uint64_t* len, uint32_t nstreams) {
   if (!e || (nstreams && (!d_data || !off || !len)) || nstreams > 65535) return BSG_EINVAL;
+  if (reinterpret_cast<uintptr_t>(d_data) % 16 != 0) return BSG_EINVAL;
+  uint64_t hi = 0;  // an empty stream's offset counts too: it is still an address in d_data
+  for (uint32_t s = 0; s < nstreams; ++s) {
+    if (off[s] % 16 != 0 || len[s] >= (1ull << 40)) return BSG_EINVAL;
+    if (off[s] > UINT64_MAX - len[s]) return BSG_EINVAL;
+    hi = std::max<uint64_t>(hi, off[s] + len[s]);
+  }
   int rc;
   if ((rc = e->setdev())) return rc;
   // the SHA-256 loader reads up to kReadSlack bytes past a stream's end (masked): that memory
   // must belong to the same allocation
-  uint64_t hi = 0;
-  for (uint32_t s = 0; s < nstreams; ++s) hi = std::max<uint64_t>(hi, off[s] + len[s]);
   if (nstreams) {
     hipDeviceptr_t base = nullptr;
     size_t size = 0;
@@ -2261,7 +2269,7 @@ static int engine_batch(bsg_engine* e, const uint8_t* d_data, const uint64_t* of
       return BSG_EINVAL;  // not a HIP device allocation
     }
     const uint64_t avail = (uint64_t)((const uint8_t*)base + size - d_data);
-    if (hi + kReadSlack > avail) {
+    if (avail < kReadSlack || hi > avail - kReadSlack) {  // (hi + kReadSlack could wrap)
       std::fprintf(stderr, "bsgpu: device buffer needs %llu readable bytes after the last "
                            "stream (has %llu)\n", (unsigned long long)kReadSlack,
                    (unsigned long long)(avail > hi ? avail - hi : 0));
@@ -2270,7 +2278,6 @@ static int engine_batch(bsg_engine* e, const uint8_t* d_data, const uint64_t* of
   }
   e->descs.assign(nstreams, StreamDesc{});
   for (uint32_t s = 0; s < nstreams; ++s) {
-    if (off[s] % 16 != 0 || len[s] >= (1ull << 40)) return BSG_EINVAL;
     StreamDesc& d = e->descs[s];
     d.data_off = off[s];
     d.len = len[s];
@@ -2957,6 +2964,10 @@ struct bsg_hasher {
                        (marks[2] - marks[1]) / 1e6);
       }
     } rep{dbg_times, t_in, n};
+    // a wrapped off + len would size the private copy below by a small `hi` and leave the
+    // kernel a wild address: refused before anything is allocated or copied
+    for (uint32_t i = 0; i < n; ++i)
+      if (o[i] > UINT64_MAX - l[i]) return BSG_EINVAL;
     hipPointerAttribute_t attr;
     bool on_device = false;
     if (hipPointerGetAttributes(&attr, base) == hipSuccess)

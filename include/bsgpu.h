@@ -159,9 +159,17 @@ int bsg_stream_stats_get(bsg_ctx* ctx, bsg_stream_stats* out);
 typedef struct bsg_engine bsg_engine;
 bsg_engine* bsg_engine_create(int device, const uint32_t* table /* 256 or NULL */, int* err);
 void bsg_engine_destroy(bsg_engine* eng);
-/* Enqueue split + hash of nstreams streams d_data[off[i] .. off[i]+len[i]) (device memory,
- * off[i] % 16 == 0; off/len are host arrays; at most 65,535 streams of < 2^40 bytes each, a
- * device-memory bound: one stream of a run lies whole in device memory).
+/* Enqueue split + hash of nstreams streams d_data[off[i] .. off[i]+len[i]) (device memory;
+ * off/len are host arrays; at most 65,535 streams of < 2^40 bytes each, a device-memory bound:
+ * one stream of a run lies whole in device memory).
+ * Layout: d_data and every off[i] are multiples of 16 (d_data is the address the kernels load
+ * from, so a base such as allocation + 4 is refused; allocation + 16 is fine). The streams may
+ * lie in any order, with gaps of any size between them, and may overlap or coincide (two
+ * streams on the same bytes, one a prefix or an inner part of another): each stream's records
+ * depend on its own bytes alone, never on the bytes around it. A zero-length stream's off[i]
+ * still counts for the allocation check below. BSG_EINVAL, before anything is enqueued, for an
+ * unaligned d_data or off[i], a len[i] >= 2^40, an off[i] + len[i] that wraps, or streams that
+ * leave less than BSG_READ_SLACK bytes of the allocation after them.
  * Asynchronous on the engine's stream (a run of >= 256 MiB hashes its two longest chunks on a
  * second pooled stream, which the engine's stream waits for before the run completes; see
  * BSG_KNOB_EARLY).
@@ -172,8 +180,9 @@ int bsg_engine_run(bsg_engine* eng, const uint8_t* d_data, const uint64_t* off,
                    const uint64_t* len, uint32_t nstreams, const bsg_params* params);
 /* Enqueue SHA-256 of nblobs whole blobs d_data[off[i] .. off[i]+len[i]) (bs.Blob.Ref,
  * bs.go:24-26, for many blobs at once: the read-side verification of split.Reader, a store's
- * batched Puts): same constraints as bsg_engine_run (device memory, off[i] % 16 == 0, at most
- * 65,535 blobs, BSG_READ_SLACK readable bytes after the last); no splitting, record i (after
+ * batched Puts): same constraints and the same layout freedom as bsg_engine_run (device memory,
+ * d_data and every off[i] multiples of 16, any order, gaps, overlapping or coinciding blobs, at
+ * most 65,535 blobs, BSG_READ_SLACK readable bytes after the last); no splitting, record i (after
  * bsg_engine_finish) carries blob i's ref, offset 0 and len[i]. Asynchronous. */
 int bsg_engine_hash(bsg_engine* eng, const uint8_t* d_data, const uint64_t* off,
                     const uint64_t* len, uint32_t nblobs);
@@ -252,7 +261,11 @@ int bsg_split_hash_batch(int device, const uint8_t* host_data, const uint64_t* o
                          uint64_t* nchunks);
 
 /* Batched SHA-256 of n blobs base[off[i] .. off[i]+len[i]); base may be host or device memory;
- * refs receives n*32 bytes (host). */
+ * refs receives n*32 bytes (host). base and off[i] need no alignment; the blobs may lie in any
+ * order, with gaps, and may overlap or coincide. base[0 .. max(off[i]+len[i])) must be readable
+ * (a small batch is copied whole, gaps included, to a private device buffer with its own read
+ * slack, so nothing past the last blob is read). BSG_EINVAL if an off[i] + len[i] wraps. The
+ * same holds for bsg_hasher_sum. */
 int bsg_sha256_batch(int device, const uint8_t* base, const uint64_t* off, const uint64_t* len,
                      uint32_t n, uint8_t* refs);
 
