@@ -223,7 +223,9 @@ typedef struct bsg_tree_node {
  * run, an unfinished or failed run). Calling it twice on one run gives the same result. */
 int bsg_engine_trees(bsg_engine* eng, uint64_t* nnodes, uint64_t* arena_bytes);
 /* Root per stream (32 bytes each; all zero for an empty stream, bs.Zero) and, if node_counts is
- * not NULL, the number of nodes per stream. */
+ * not NULL, the number of nodes per stream. nstreams may be smaller than the run's: the first
+ * nstreams streams are written and nothing past them; larger is BSG_EINVAL. BSG_ESTATE without
+ * a tree (as the device pointers below are NULL). */
 int bsg_engine_copy_roots(bsg_engine* eng, uint8_t* roots, uint64_t* node_counts, uint32_t nstreams);
 /* Node records (up to cap) and the blob arena (up to arena_cap bytes) to host memory. */
 int bsg_engine_copy_tree_nodes(bsg_engine* eng, bsg_tree_node* out, uint64_t cap,

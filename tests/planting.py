@@ -22,6 +22,9 @@ draw in which no position of the layout's "clean" ranges but the planted ends ha
 before a planted end is the only thing that keeps the end from being a boundary, and at
 Bits = 12 a batch of a thousand streams always has some, so the seed is chosen per stream.
 test_planting_cpu.py checks the outcome against the oracle.
+
+level_windows() and level_stream() (at the end) serve the tree tests (tree_cases.py): streams cut
+into chunks of chosen levels.
 """
 import numpy as np
 
@@ -427,3 +430,85 @@ def greedy_walk(cands, n, min_size):
 
 def chunk_ends(chunks):
     return [int(c["offset"]) + int(c["len"]) - 1 for c in chunks]
+
+
+# ---------------------------------------------------------------------------------------------
+# Chunks of chosen levels (the tree tests): 64-byte windows written back to back
+# ---------------------------------------------------------------------------------------------
+# At MinSize 64 a stream made of planted 64-byte windows written back to back is cut into exactly
+# those windows: every other position lies less than MinSize after the previous boundary, so
+# chunk i is window i, 64 bytes, with level tz(hash(window i)) - Bits.
+#
+# A window with a chosen hash is built, not searched. Bytes i and i + 32 of a window are rotated
+# alike (k = 63 - i and k - 32), so a window whose two halves are equal hashes to 0 (tz = 32).
+# Replacing bytes 31, 63 by (a, b) and bytes 31 - r, 63 - r by (c, d) gives
+#   h = (T[a] ^ T[b]) ^ rotl(T[c] ^ T[d], r),
+# and among the 32,640 x 32,640 x 31 choices some pair meets any 32-bit target (found by lookup).
+_LEVEL_POOL = {}
+LEVEL_POOL = 2                    # distinct windows per level
+
+
+def _pair_xors(T):
+    a, b = np.triu_indices(256, 1)
+    d = T[a] ^ T[b]
+    order = np.argsort(d, kind="stable")
+    return d[order], a[order].astype(np.uint8), b[order].astype(np.uint8)
+
+
+def window_with_hash(table, target, seed):
+    """One 64-byte window whose window hash is exactly `target`."""
+    T = np.asarray(table, dtype=np.uint32)
+    rng = np.random.default_rng([4242, int(target), seed])
+    half = rng.integers(0, 256, 32, dtype=np.uint8)
+    w = np.concatenate([half, half])
+    if target == 0:
+        return w
+    d, a, b = _pair_xors(T)
+    for r in rng.permutation(np.arange(1, 32)):
+        want = np.uint32(target) ^ _rotl(d, int(r))      # T[a] ^ T[b] for every (c, d)
+        at = np.searchsorted(d, want)
+        hit = np.nonzero(d[np.minimum(at, len(d) - 1)] == want)[0]
+        if len(hit):
+            j = int(hit[rng.integers(0, len(hit))])
+            i = int(at[j])
+            w[31], w[63] = a[i], b[i]
+            w[31 - r], w[63 - r] = a[j], b[j]
+            return w
+    raise AssertionError(("no window", hex(int(target))))
+
+
+def level_windows(table, bits, levels):
+    """{level: [LEVEL_POOL, 64] uint8}: distinct windows whose hash has exactly bits + level
+    trailing zeros (a zero hash, tz = 32, for level 32 - bits), for every level in `levels`."""
+    out = {}
+    for lv in sorted(set(int(x) for x in levels)):
+        tz = bits + lv
+        assert 0 <= lv and tz <= 32, (bits, lv)
+        key = (np.asarray(table).tobytes(), tz)
+        if key not in _LEVEL_POOL:
+            rng = np.random.default_rng([77, tz])
+            wins = []
+            while len(wins) < LEVEL_POOL:
+                # any odd multiple of 2^tz has exactly tz trailing zeros
+                odd = int(rng.integers(0, 1 << (31 - tz))) * 2 + 1 if tz < 31 else 1
+                target = (odd << tz) & 0xFFFFFFFF if tz < 32 else 0
+                w = window_with_hash(table, target, len(wins))
+                h = window_hashes(table, w, 63, 64)
+                assert int(_tz(h)[0]) == tz, (tz, hex(int(h[0])))
+                if not any((w == x).all() for x in wins):
+                    wins.append(w)
+            _LEVEL_POOL[key] = np.stack(wins)
+        out[lv] = _LEVEL_POOL[key]
+    return out
+
+
+def level_stream(table, bits, levels):
+    """A stream that Bits = bits / MinSize = 64 cuts into len(levels) chunks of 64 bytes, chunk i
+    of level levels[i]: the level's windows from the pool in turn, back to back."""
+    levels = np.asarray(levels, dtype=np.int64)
+    pool = level_windows(table, bits, np.unique(levels))
+    out = np.zeros((len(levels), 64), dtype=np.uint8)
+    for lv, wins in pool.items():
+        at = np.nonzero(levels == lv)[0]
+        out[at] = wins[np.arange(len(at)) % len(wins)]
+    return out.reshape(-1)

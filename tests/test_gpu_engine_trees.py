@@ -70,6 +70,7 @@ def _check_nodes(oracle, data, recs, fanout, root, snodes, arena):
     assert [nd["ref"].tobytes() for nd in snodes] == [f["ref"] for f in form]
     if len(snodes):
         assert snodes[-1]["ref"].tobytes() == root
+    TF.check_listing(recs, fanout, root, snodes, arena)
     return want
 
 
