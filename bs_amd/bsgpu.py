@@ -142,6 +142,21 @@ def lib() -> ctypes.CDLL:
         "bsg_engine_tree_arena_device": (vp, [vp]),
         "bsg_engine_roots_device": (vp, [vp]),
         "bsg_engine_trees_ms_debug": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_float)]),
+        "bsg_refset_new": (vp, [ctypes.c_int, ctypes.POINTER(ctypes.c_int)]),
+        "bsg_refset_free": (None, [vp]),
+        "bsg_refset_count": (ctypes.c_uint64, [vp]),
+        "bsg_refset_add": (ctypes.c_int, [vp, vp, ctypes.c_uint64, vp]),
+        "bsg_engine_dedup": (ctypes.c_int, [vp, vp, u64p, u64p]),
+        "bsg_engine_copy_dedup": (ctypes.c_int, [vp, vp, ctypes.c_uint64, vp, vp,
+                                                 ctypes.c_uint64]),
+        "bsg_engine_dedup_first_device": (vp, [vp]),
+        "bsg_engine_dedup_uniq_device": (vp, [vp]),
+        "bsg_engine_dedup_pack_off_device": (vp, [vp]),
+        "bsg_engine_pack_unique": (ctypes.c_int, [vp, vp, ctypes.c_uint64]),
+        "bsg_engine_dedup_ms_debug": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_float)]),
+        "bsg_engine_pack_mode_debug": (ctypes.c_int, [vp, ctypes.c_int]),
+        "bsg_engine_d2d_ms_debug": (ctypes.c_int, [vp, vp, vp, ctypes.c_uint64,
+                                                   ctypes.POINTER(ctypes.c_float)]),
         "bsg_engine_candidates": (ctypes.c_uint64, [vp]),
         "bsg_engine_profile": (ctypes.c_int, [vp, ctypes.c_int]),
         "bsg_engine_diag": (ctypes.c_int, [vp, u64p]),
@@ -550,6 +565,36 @@ class Engine:
         return {"layout": float(out[0]), "emit": float(out[1]), "hash": float(out[2]),
                 "total": float(out[3])}
 
+    def dedup(self, refset: "RefSet | None" = None):
+        """bsg_engine_dedup: first occurrence per ref over the last finished run's records, on
+        the device. Returns (first[n], uniq[nunique], pack_off[nunique + 1]) as uint64 arrays:
+        record i is new iff first[i] == i (bit 63, IN_SET, marks a ref `refset` already held).
+        With a refset the new refs are in it afterwards. Sets nunique and unique_bytes."""
+        nu, nb = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        _check(lib().bsg_engine_dedup(self.h, refset.h if refset is not None else None,
+                                      ctypes.byref(nu), ctypes.byref(nb)), "bsg_engine_dedup")
+        self.nunique, self.unique_bytes = nu.value, nb.value
+        first = np.zeros(max(self.nchunks, 1), dtype=np.uint64)
+        uniq = np.zeros(max(nu.value, 1), dtype=np.uint64)
+        pack_off = np.zeros(nu.value + 1, dtype=np.uint64)
+        _check(lib().bsg_engine_copy_dedup(self.h, first.ctypes.data, self.nchunks,
+                                           uniq.ctypes.data, pack_off.ctypes.data, nu.value),
+               "bsg_engine_copy_dedup")
+        return first[: self.nchunks], uniq[: nu.value], pack_off
+
+    def pack_unique(self, buf: "DeviceBuffer", offset: int = 0, cap: int | None = None) -> None:
+        """bsg_engine_pack_unique: the new records' bytes, contiguous, into buf (device memory)
+        from `offset` on: buf[offset + pack_off[k] : offset + pack_off[k + 1]] = record uniq[k]."""
+        cap = buf.nbytes - offset if cap is None else cap
+        _check(lib().bsg_engine_pack_unique(self.h, buf.ptr + offset, cap),
+               "bsg_engine_pack_unique")
+
+    def dedup_ms(self) -> dict:
+        """The last dedup() and pack_unique() calls in ms (test tooling; needs profile() on)."""
+        out = (ctypes.c_float * 2)()
+        _check(lib().bsg_engine_dedup_ms_debug(self.h, out), "bsg_engine_dedup_ms_debug")
+        return {"dedup": float(out[0]), "pack": float(out[1])}
+
     @property
     def stream(self) -> int:
         return lib().bsg_engine_stream(self.h) or 0
@@ -628,6 +673,44 @@ class Engine:
     def __del__(self):
         try:
             self.close()
+        except Exception:
+            pass
+
+
+IN_SET = 1 << 63  # Engine.dedup: first[i] bit 63, the ref was in the refset before the call
+
+
+class RefSet:
+    """bsg_refset: the refs a store already holds, kept on the device across runs."""
+
+    def __init__(self, device: int = 0):
+        err = ctypes.c_int(0)
+        self.h = lib().bsg_refset_new(device, ctypes.byref(err))
+        if not self.h:
+            raise BsgError(err.value, "bsg_refset_new")
+
+    def add(self, refs) -> np.ndarray:
+        """bsg_refset_add: refs as an (n, 32) uint8 array or a list of 32-byte strings. Returns
+        added[n] (uint8): 1 iff the ref was not in the set and is no earlier entry of this call."""
+        if not isinstance(refs, np.ndarray):
+            refs = np.frombuffer(b"".join(bytes(r) for r in refs), dtype=np.uint8)
+        a = np.ascontiguousarray(refs, dtype=np.uint8).reshape(-1, 32)
+        added = np.zeros(max(len(a), 1), dtype=np.uint8)
+        _check(lib().bsg_refset_add(self.h, a.ctypes.data, len(a), added.ctypes.data),
+               "bsg_refset_add")
+        return added[: len(a)]
+
+    def count(self) -> int:
+        return int(lib().bsg_refset_count(self.h))
+
+    def free(self) -> None:
+        if self.h:
+            lib().bsg_refset_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
         except Exception:
             pass
 

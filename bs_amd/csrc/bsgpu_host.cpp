@@ -434,7 +434,164 @@ int device_error(uint64_t code) {
   return BSG_EDEVICE;
 }
 
+// an allocation the dedup code reports as BSG_ENOMEM (the caller's state is still unchanged)
+#define MCHECK(x)                           \
+  do {                                      \
+    if ((x) != hipSuccess) {                \
+      (void)hipGetLastError();              \
+      return BSG_ENOMEM;                    \
+    }                                       \
+  } while (0)
+
+uint64_t pow2_at_least(uint64_t v) {
+  uint64_t p = 1;
+  while (p < v) p <<= 1;
+  return p;
+}
+
+// The buffers of one first-occurrence pass (launch_dedup) over n items, and its results. An
+// engine owns one for bsg_engine_dedup, a set one for bsg_refset_add.
+struct DedupWork {
+  DevBuf tab, first, rank, bpre, uniq, pack_off, part, hdr;
+  PinBuf h_hdr;
+  DedupHdr last{};
+
+  void release() {
+    DevBuf* bufs[] = {&tab, &first, &rank, &bpre, &uniq, &pack_off, &part, &hdr};
+    for (DevBuf* b : bufs) b->release();
+    h_hdr.release();
+  }
+
+  int reserve(uint64_t n, uint64_t* slots) {
+    const uint64_t n1 = n ? n : 1;
+    *slots = pow2_at_least(std::max<uint64_t>(64, 2 * n1));
+    MCHECK(tab.ensure(8 * *slots));
+    MCHECK(first.ensure(8 * n1));
+    MCHECK(rank.ensure(8 * (n1 + 1)));
+    MCHECK(bpre.ensure(8 * (n1 + 1)));
+    MCHECK(uniq.ensure(8 * n1));
+    MCHECK(pack_off.ensure(8 * (n1 + 1)));
+    MCHECK(part.ensure(8 * tree_scan_parts(n1)));
+    MCHECK(hdr.ensure(sizeof(DedupHdr)));
+    MCHECK(h_hdr.ensure(sizeof(DedupHdr)));
+    return BSG_OK;
+  }
+
+  DedupArgs args(const uint8_t* refs, uint64_t stride, const uint8_t* lens, uint64_t len_stride,
+                 uint64_t n, uint64_t slots) const {
+    DedupArgs a{};
+    a.refs = refs;
+    a.stride = stride;
+    a.lens = lens;
+    a.len_stride = len_stride;
+    a.n = n;
+    a.tab = tab.as<uint64_t>();
+    a.tab_mask = slots - 1;
+    a.first = first.as<uint64_t>();
+    a.rank = rank.as<uint64_t>();
+    a.bpre = bpre.as<uint64_t>();
+    a.uniq = uniq.as<uint64_t>();
+    a.pack_off = pack_off.as<uint64_t>();
+    a.part = part.as<uint64_t>();
+    a.hdr = hdr.as<DedupHdr>();
+    return a;
+  }
+
+  // the header to the host after everything enqueued on s; BSG_EDEVICE if a device check failed
+  int readback(hipStream_t s) {
+    HCHECK(hipMemcpyAsync(h_hdr.p, hdr.p, sizeof(DedupHdr), hipMemcpyDeviceToHost, s));
+    HCHECK(stream_wait(s));
+    last = *h_hdr.as<DedupHdr>();
+    if (last.error) {
+      std::fprintf(stderr, "bsgpu: dedup sanity check failed (code %llu)\n",
+                   (unsigned long long)last.error);
+      return BSG_EDEVICE;
+    }
+    return BSG_OK;
+  }
+};
+
 }  // namespace
+
+// A set of 32-byte refs on one device: an append-only key array and an open-addressing table of
+// key indices (bsgpu_dedup.inc). Every entry point takes `mu`, so engines on several threads may
+// share a set; each call has synchronised the stream it used before it lets go.
+struct bsg_refset {
+  int dev = 0;
+  int num_cus = 256;
+  hipStream_t stream = nullptr;  // bsg_refset_add's own
+  std::mutex mu;
+  DevBuf keys, tab;
+  uint64_t slots = 0;            // of tab (a power of two)
+  uint64_t key_cap = 0;          // keys the key array holds
+  std::atomic<uint64_t> count{0};
+  bool dead = false;             // a device error: BSG_ESTATE from then on
+  DevBuf staged;                 // bsg_refset_add: the caller's refs
+  DedupWork work;
+
+  // the set's part of a first-occurrence pass
+  void lookup_args(DedupArgs* a) const {
+    a->set_keys = keys.as<uint8_t>();
+    a->set_tab = tab.as<uint64_t>();
+    a->set_mask = slots - 1;
+    a->set_count = count.load();
+  }
+
+  // The m new items of a finished pass `d` (its uniq[0 .. m)) become keys, on stream s: the key
+  // array and the table grow first (doubling, the table rehashed on the device), and nothing of
+  // the set changes unless every allocation succeeded. Synchronises s and reads the pass's
+  // header (`w`) back once more for its error word.
+  int add_new(const DedupArgs& d, uint64_t m, DedupWork* w, hipStream_t s) {
+    if (!m) return BSG_OK;
+    const uint64_t cnt = count.load(), want = cnt + m;
+    uint64_t nslots = slots;
+    while (want * 100 > nslots * kRefSetLoadPct) nslots <<= 1;
+    uint64_t ncap = key_cap;
+    while (ncap < want) ncap <<= 1;
+    DevBuf ntab, nkeys;
+    if (nslots != slots) MCHECK(ntab.ensure(8 * nslots));
+    if (ncap != key_cap && nkeys.ensure(32 * ncap) != hipSuccess) {
+      (void)hipGetLastError();
+      ntab.release();
+      return BSG_ENOMEM;
+    }
+    SetArgs sa{};
+    sa.keys = nkeys.p ? nkeys.as<uint8_t>() : keys.as<uint8_t>();
+    sa.tab = ntab.p ? ntab.as<uint64_t>() : tab.as<uint64_t>();
+    sa.mask = nslots - 1;
+    sa.count = cnt;
+    sa.hdr = d.hdr;
+    hipError_t e = hipSuccess;
+    if (nkeys.p && cnt)
+      e = hipMemcpyAsync(nkeys.p, keys.p, 32 * cnt, hipMemcpyDeviceToDevice, s);
+    if (e == hipSuccess && ntab.p) {
+      e = hipMemsetAsync(ntab.p, 0xFF, 8 * nslots, s);
+      if (e == hipSuccess) e = launch_set_rehash(sa, s, num_cus);
+    }
+    if (e == hipSuccess) e = launch_set_add(sa, d, m, s, num_cus);
+    int rc = e == hipSuccess ? w->readback(s) : BSG_EDEVICE;
+    if (rc) {  // the old table may hold indices of keys that never arrived
+      (void)hipGetLastError();
+      (void)hipStreamSynchronize(s);
+      ntab.release();
+      nkeys.release();
+      dead = true;
+      return rc;
+    }
+    if (ntab.p) {
+      tab.release();
+      tab = ntab;
+      slots = nslots;
+    }
+    if (nkeys.p) {
+      keys.release();
+      keys = nkeys;
+      key_cap = ncap;
+    }
+    count.store(want);
+    return BSG_OK;
+  }
+};
 
 struct bsg_engine {
   int dev = 0;
@@ -490,6 +647,15 @@ struct bsg_engine {
   bool tree_valid = false;
   std::vector<hipEvent_t> tev;  // profile: start, layout done, per height emit / hash done, end
   float tree_ms[4] = {0, 0, 0, 0};  // profile: counting + layout, emit, hash, whole call
+
+  // bsg_engine_dedup / bsg_engine_pack_unique: which records of the last finished split run are
+  // new, and their bytes packed. The dedup work owns every buffer in `dd` and reads the records.
+  DedupWork dd;
+  bool dd_valid = false;      // `dd` holds the current run's result
+  uint64_t dd_n = 0, dd_nunique = 0, dd_bytes = 0;
+  bool pack_funnel = false;   // measurement tooling: the aligned-load variant of k_pack
+  hipEvent_t dd_ev[4] = {nullptr, nullptr, nullptr, nullptr};  // profile: dedup, pack
+  float dd_ms[2] = {0, 0};
 
   // Round 5: a lightly loaded run (at most BSG_KNOB_LIGHT_BYTES, default 4 GiB, where the
   // longest chunk's chain is the step: configs[1], [3], [4]) keeps its early chains on the
@@ -828,6 +994,7 @@ struct bsg_engine {
   int enqueue() {
     int rc;
     run_done = false;
+    dd_valid = false;  // a dedup result belongs to the run it was made from
     if (early_open) {  // a failed run left second-stream work its engine stream never waited for
       HCHECK(hipStreamSynchronize(estream));
       early_open = false;
@@ -854,6 +1021,7 @@ struct bsg_engine {
   int enqueue_hash() {
     int rc;
     run_done = false;
+    dd_valid = false;  // a dedup result belongs to the run it was made from
     const RunPlan pl = plan_hash();
     if ((rc = reserve(pl)) || (rc = run_start(pl, stream))) return rc;
     mark(0);
@@ -1079,6 +1247,99 @@ struct bsg_engine {
     }
     tree = tp;
     tree_valid = true;
+    return BSG_OK;
+  }
+
+  void dd_mark(int i) {
+    if (!profile) return;
+    if (!dd_ev[i] && hipEventCreate(&dd_ev[i]) != hipSuccess) {
+      (void)hipGetLastError();
+      dd_ev[i] = nullptr;
+    }
+    if (dd_ev[i]) (void)hipEventRecord(dd_ev[i], stream);
+  }
+  void dd_elapsed(int k) {
+    dd_ms[k] = 0.f;
+    if (profile && dd_ev[2 * k] && dd_ev[2 * k + 1] &&
+        hipEventElapsedTime(&dd_ms[k], dd_ev[2 * k], dd_ev[2 * k + 1]) != hipSuccess) {
+      (void)hipGetLastError();
+      dd_ms[k] = 0.f;
+    }
+  }
+
+  // first occurrence per ref over the run's records (and `set`), then the new refs into the set
+  int dedup(bsg_refset* set) {
+    if (!run_done || snapshot || hash_mode) return BSG_ESTATE;
+    dd_valid = false;
+    std::unique_lock<std::mutex> lk;
+    if (set) {
+      lk = std::unique_lock<std::mutex>(set->mu);
+      if (set->dead) return BSG_ESTATE;
+    }
+    int rc;
+    const uint64_t n = last.nchunks;
+    uint64_t slots = 0;
+    if ((rc = dd.reserve(n, &slots))) return rc;
+    dd_mark(0);
+    HCHECK(hipMemsetAsync(dd.hdr.p, 0, sizeof(DedupHdr), stream));
+    const uint8_t* rec = out.as<uint8_t>();
+    DedupArgs a = dd.args(rec + offsetof(ChunkRec, ref), sizeof(ChunkRec),
+                          rec + offsetof(ChunkRec, len), sizeof(ChunkRec), n, slots);
+    if (set) set->lookup_args(&a);
+    if (n) {
+      HCHECK(hipMemsetAsync(dd.tab.p, 0xFF, 8 * slots, stream));
+      HCHECK(dbg("launch_dedup", stream, launch_dedup(a, stream, num_cus)));
+    } else {
+      HCHECK(hipMemsetAsync(dd.pack_off.p, 0, 8, stream));
+    }
+    if ((rc = dd.readback(stream))) return rc;
+    const DedupHdr h = dd.last;
+    if (h.nunique > n) return BSG_EDEVICE;
+    if (set && (rc = set->add_new(a, h.nunique, &dd, stream))) return rc;
+    dd_mark(1);
+    if (profile) {
+      HCHECK(stream_wait(stream));
+      dd_elapsed(0);
+    }
+    dd_n = n;
+    dd_nunique = h.nunique;
+    dd_bytes = h.unique_bytes;
+    dd_valid = true;
+    return BSG_OK;
+  }
+
+  // bytes from d_data to the end of the run's last stream
+  uint64_t run_span() const {
+    uint64_t hi = 0;
+    for (const StreamDesc& d : descs) hi = std::max<uint64_t>(hi, d.data_off + d.len);
+    return hi;
+  }
+
+  int pack_unique(uint8_t* d_out, uint64_t cap) {
+    if (!dd_valid || !run_done) return BSG_ESTATE;
+    if (!d_out || reinterpret_cast<uintptr_t>(d_out) % 16 != 0 || cap < dd_bytes) return BSG_EINVAL;
+    const uintptr_t o0 = reinterpret_cast<uintptr_t>(d_out), o1 = o0 + dd_bytes;
+    const uintptr_t s0 = reinterpret_cast<uintptr_t>(d_data), s1 = s0 + run_span();
+    if (o1 < o0 || (dd_bytes && o0 < s1 && s0 < o1)) return BSG_EINVAL;
+    PackArgs a{};
+    a.data = d_data;
+    a.streams = streams.as<StreamDesc>();
+    a.nstreams = nstreams;
+    a.rec = out.as<ChunkRec>();
+    a.nrec = dd_n;
+    a.uniq = dd.uniq.as<uint64_t>();
+    a.pack_off = dd.pack_off.as<uint64_t>();
+    a.nunique = dd_nunique;
+    a.total = dd_bytes;
+    a.out = d_out;
+    a.hdr = dd.hdr.as<DedupHdr>();
+    dd_mark(2);
+    HCHECK(hipMemsetAsync(dd.hdr.p, 0, sizeof(DedupHdr), stream));
+    HCHECK(dbg("launch_pack", stream, launch_pack(a, pack_funnel, stream)));
+    dd_mark(3);
+    int rc;
+    if ((rc = dd.readback(stream))) return rc;
+    dd_elapsed(1);
     return BSG_OK;
   }
 };
@@ -2216,6 +2477,9 @@ void bsg_engine_destroy(bsg_engine* e) {
                      &e->t_descs, &e->t_arena, &e->t_nodes, &e->t_roots, &e->t_ncount};
   for (DevBuf* b : tbufs) b->release();
   e->h_thdr.release();
+  e->dd.release();
+  for (hipEvent_t ev : e->dd_ev)
+    if (ev) hipEventDestroy(ev);
   for (hipEvent_t ev : e->tev)
     if (ev) hipEventDestroy(ev);
   // a failed run may have left early chains (k_pick / k_early on estream) that the engine
@@ -2397,6 +2661,182 @@ const uint8_t* bsg_engine_tree_arena_device(const bsg_engine* e) {
 
 const uint8_t* bsg_engine_roots_device(const bsg_engine* e) {
   return e && e->tree_valid && e->run_done ? e->t_roots.as<uint8_t>() : nullptr;
+}
+
+int bsg_engine_dedup(bsg_engine* e, bsg_refset* set, uint64_t* nunique, uint64_t* unique_bytes) {
+  if (!e || !nunique || !unique_bytes || (set && set->dev != e->dev)) return BSG_EINVAL;
+  int rc = e->setdev();
+  if (rc) return rc;
+  if ((rc = e->dedup(set))) return rc;
+  *nunique = e->dd_nunique;
+  *unique_bytes = e->dd_bytes;
+  return BSG_OK;
+}
+
+int bsg_engine_copy_dedup(bsg_engine* e, uint64_t* first, uint64_t cap_first, uint64_t* uniq,
+                          uint64_t* pack_off, uint64_t cap_uniq) {
+  if (!e) return BSG_EINVAL;
+  if (!e->dd_valid || !e->run_done) return BSG_ESTATE;
+  int rc = e->setdev();
+  if (rc) return rc;
+  const uint64_t nf = std::min<uint64_t>(cap_first, e->dd_n);
+  const uint64_t nu = std::min<uint64_t>(cap_uniq, e->dd_nunique);
+  if (first && nf) HCHECK(hipMemcpy(first, e->dd.first.p, 8 * nf, hipMemcpyDeviceToHost));
+  if (uniq && nu) HCHECK(hipMemcpy(uniq, e->dd.uniq.p, 8 * nu, hipMemcpyDeviceToHost));
+  if (pack_off) HCHECK(hipMemcpy(pack_off, e->dd.pack_off.p, 8 * (nu + 1), hipMemcpyDeviceToHost));
+  return BSG_OK;
+}
+
+const uint64_t* bsg_engine_dedup_first_device(const bsg_engine* e) {
+  return e && e->dd_valid && e->run_done ? e->dd.first.as<uint64_t>() : nullptr;
+}
+
+const uint64_t* bsg_engine_dedup_uniq_device(const bsg_engine* e) {
+  return e && e->dd_valid && e->run_done ? e->dd.uniq.as<uint64_t>() : nullptr;
+}
+
+const uint64_t* bsg_engine_dedup_pack_off_device(const bsg_engine* e) {
+  return e && e->dd_valid && e->run_done ? e->dd.pack_off.as<uint64_t>() : nullptr;
+}
+
+int bsg_engine_pack_unique(bsg_engine* e, uint8_t* d_out, uint64_t cap) {
+  if (!e) return BSG_EINVAL;
+  int rc = e->setdev();
+  if (rc) return rc;
+  return e->pack_unique(d_out, cap);
+}
+
+// Test and measurement tooling (not in bsgpu.h): the last bsg_engine_dedup and
+// bsg_engine_pack_unique calls in ms, timed with HIP events on the engine stream when
+// bsg_engine_profile is on; the pack kernel's load variant (1: aligned loads and a byte funnel);
+// one hipMemcpyDtoDAsync of n bytes on the engine stream timed the same way.
+extern "C" int bsg_engine_dedup_ms_debug(const bsg_engine* e, float out[2]) {
+  if (!e || !out) return BSG_EINVAL;
+  if (!e->profile || !e->dd_valid) return BSG_ESTATE;
+  out[0] = e->dd_ms[0];
+  out[1] = e->dd_ms[1];
+  return BSG_OK;
+}
+
+extern "C" int bsg_engine_pack_mode_debug(bsg_engine* e, int funnel) {
+  if (!e || funnel < 0 || funnel > 1) return BSG_EINVAL;
+  e->pack_funnel = funnel != 0;
+  return BSG_OK;
+}
+
+extern "C" int bsg_engine_d2d_ms_debug(bsg_engine* e, void* dst, const void* src, uint64_t n,
+                                       float* ms) {
+  if (!e || !dst || !src || !ms) return BSG_EINVAL;
+  int rc = e->setdev();
+  if (rc) return rc;
+  hipEvent_t a = nullptr, b = nullptr;
+  HCHECK(hipEventCreate(&a));
+  if (hipEventCreate(&b) != hipSuccess) {
+    (void)hipGetLastError();
+    (void)hipEventDestroy(a);
+    return BSG_EDEVICE;
+  }
+  hipError_t err = hipEventRecord(a, e->stream);
+  if (err == hipSuccess)
+    err = hipMemcpyDtoDAsync((hipDeviceptr_t)dst, (hipDeviceptr_t)src, n, e->stream);
+  if (err == hipSuccess) err = hipEventRecord(b, e->stream);
+  if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
+  if (err == hipSuccess) err = hipEventElapsedTime(ms, a, b);
+  (void)hipEventDestroy(a);
+  (void)hipEventDestroy(b);
+  if (err != hipSuccess) (void)hipGetLastError();
+  return herr(err);
+}
+
+// ---- bsg_refset ---------------------------------------------------------------------------
+bsg_refset* bsg_refset_new(int device, int* err) {
+  int dummy;
+  if (!err) err = &dummy;
+  int n = 0;
+  if (hipGetDeviceCount(&n) != hipSuccess) {
+    (void)hipGetLastError();
+    n = 0;
+  }
+  if (device < 0 || device >= n) {
+    *err = BSG_ENODEV;
+    return nullptr;
+  }
+  bsg_refset* s = new (std::nothrow) bsg_refset();
+  if (!s) {
+    *err = BSG_ENOMEM;
+    return nullptr;
+  }
+  s->dev = device;
+  *err = BSG_EDEVICE;
+  if (hipSetDevice(device) == hipSuccess && stream_acquire(device, &s->stream) == hipSuccess) {
+    s->num_cus = device_cus(device);
+    s->slots = kRefSetSlots0;
+    s->key_cap = kRefSetSlots0;
+    *err = BSG_ENOMEM;
+    if (s->tab.ensure(8 * s->slots) == hipSuccess && s->keys.ensure(32 * s->key_cap) == hipSuccess) {
+      *err = herr(hipMemset(s->tab.p, 0xFF, 8 * s->slots));
+      if (*err == BSG_OK) return s;
+    }
+  }
+  (void)hipGetLastError();
+  bsg_refset_free(s);
+  return nullptr;
+}
+
+void bsg_refset_free(bsg_refset* s) {
+  if (!s) return;
+  hipSetDevice(s->dev);
+  if (s->stream) {
+    hipStreamSynchronize(s->stream);
+    stream_release(s->dev, s->stream);
+  }
+  s->keys.release();
+  s->tab.release();
+  s->staged.release();
+  s->work.release();
+  delete s;
+}
+
+uint64_t bsg_refset_count(const bsg_refset* s) { return s ? s->count.load() : 0; }
+
+int bsg_refset_add(bsg_refset* s, const uint8_t* refs, uint64_t n, uint8_t* added) {
+  if (!s || (n && !refs) || n > (1ull << 40)) return BSG_EINVAL;
+  std::lock_guard<std::mutex> g(s->mu);
+  if (s->dead) return BSG_ESTATE;
+  HCHECK(hipSetDevice(s->dev));
+  if (!n) return BSG_OK;
+  int rc;
+  uint64_t slots = 0;
+  if ((rc = s->work.reserve(n, &slots))) return rc;
+  MCHECK(s->staged.ensure(32 * n));
+  HCHECK(hipMemcpyAsync(s->staged.p, refs, 32 * n, hipMemcpyHostToDevice, s->stream));
+  HCHECK(hipMemsetAsync(s->work.hdr.p, 0, sizeof(DedupHdr), s->stream));
+  HCHECK(hipMemsetAsync(s->work.tab.p, 0xFF, 8 * slots, s->stream));
+  DedupArgs a = s->work.args(s->staged.as<uint8_t>(), 32, nullptr, 0, n, slots);
+  s->lookup_args(&a);
+  HCHECK(dbg("launch_dedup", s->stream, launch_dedup(a, s->stream, s->num_cus)));
+  if ((rc = s->work.readback(s->stream))) {
+    if (rc == BSG_EDEVICE) s->dead = true;
+    return rc;
+  }
+  const uint64_t m = s->work.last.nunique;
+  if (m > n) {
+    s->dead = true;
+    return BSG_EDEVICE;
+  }
+  std::vector<uint64_t> first;
+  if (added) {
+    try {
+      first.resize(n);
+    } catch (const std::bad_alloc&) {
+      return BSG_ENOMEM;
+    }
+    HCHECK(hipMemcpy(first.data(), s->work.first.p, 8 * n, hipMemcpyDeviceToHost));
+  }
+  if ((rc = s->add_new(a, m, &s->work, s->stream))) return rc;
+  if (added)
+    for (uint64_t i = 0; i < n; ++i) added[i] = first[i] == i ? 1 : 0;
+  return BSG_OK;
 }
 
 int bsg_engine_profile(bsg_engine* e, int enable) {

@@ -206,4 +206,19 @@ struct TreeNodeMeta {          // per internal id (height-major, then stream, th
   uint32_t stream;
 };
 
+// Chunk dedup on the device (bsg_engine_dedup, bsg_refset; bsgpu_dedup.inc). The tables are open
+// addressing with linear probing; a slot holds an index (of a record of the run, or of a key in a
+// set's append-only key array), never a key, and kDedupEmpty marks a free slot.
+constexpr uint64_t kDedupEmpty = ~0ull;
+constexpr uint64_t kDedupInSet = 1ull << 63;  // first[i]: the ref was in the set before the call
+constexpr uint64_t kRefSetSlots0 = 1024;      // a new set's table
+constexpr uint64_t kRefSetLoadPct = 50;       // a set's table doubles before keys * 100 > slots * this
+constexpr uint32_t kPackTile = 32768;         // output bytes per workgroup of bsg_engine_pack_unique
+struct DedupHdr {              // totals of one dedup pass, read back by the host
+  uint64_t error;              // a probe ran through its whole table (bug guard; result invalid)
+  uint64_t nunique;
+  uint64_t unique_bytes;
+  uint64_t pad_;
+};
+
 }  // namespace bsg

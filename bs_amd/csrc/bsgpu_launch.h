@@ -198,4 +198,64 @@ hipError_t launch_tree_refs(const TreeArgs& a, uint64_t u0, uint32_t n, const Ch
                             const Counters* hctr, hipStream_t s, int num_cus);
 hipError_t launch_tree_roots(const TreeArgs& a, hipStream_t s, int num_cus);
 
+// bsg_engine_dedup / bsg_refset_add (bsgpu_dedup.inc): the first occurrence of every 32-byte ref
+// among n items (a run's records, or refs a caller handed in) and in a set. Item i's ref is the
+// 32 bytes at refs + i * stride (8-byte aligned); its length the u64 at lens + i * len_stride
+// (null: 0). Nothing here writes the items.
+struct DedupArgs {
+  const uint8_t* refs;
+  uint64_t stride;
+  const uint8_t* lens;
+  uint64_t len_stride;
+  uint64_t n;
+  uint64_t* tab;             // [tab_mask + 1] the call's own table of item indices, kDedupEmpty-filled
+  uint64_t tab_mask;
+  const uint8_t* set_keys;   // the set before the call (null: none): its keys, 32 bytes each,
+  const uint64_t* set_tab;   // and its table of key indices
+  uint64_t set_mask;
+  uint64_t set_count;
+  uint64_t* first;           // [n] smallest index with the same ref | kDedupInSet
+  uint64_t* rank;            // [n + 1] exclusive prefix of "item i is new"
+  uint64_t* bpre;            // [n + 1] exclusive prefix of the new items' lengths
+  uint64_t* uniq;            // [nunique] the new items, ascending
+  uint64_t* pack_off;        // [nunique + 1] exclusive prefix of their lengths
+  uint64_t* part;            // [tree_scan_parts(n)] workgroup sums of a prefix pass
+  DedupHdr* hdr;
+};
+hipError_t launch_dedup(const DedupArgs& a, hipStream_t s, int num_cus);
+
+// A set's table and key array. launch_set_rehash: every key index [0, count) into the
+// (kDedupEmpty-filled) table. launch_set_add: the m new items uniq[0 .. m) of `d` become keys
+// [count, count + m) and enter the table; they are distinct from each other and from every key
+// of the set (launch_dedup's result), so no key is compared.
+struct SetArgs {
+  uint8_t* keys;
+  uint64_t* tab;
+  uint64_t mask;
+  uint64_t count;
+  DedupHdr* hdr;
+};
+hipError_t launch_set_rehash(const SetArgs& a, hipStream_t s, int num_cus);
+hipError_t launch_set_add(const SetArgs& a, const DedupArgs& d, uint64_t m, hipStream_t s,
+                          int num_cus);
+
+// bsg_engine_pack_unique: out[pack_off[k] .. pack_off[k + 1]) = the bytes of record uniq[k],
+// data + streams[rec.stream].data_off + rec.offset. out is 16-byte aligned; nothing outside
+// [out, out + total) is written. funnel: aligned 16-byte loads and a byte shift instead of
+// unaligned 16-byte loads.
+struct PackArgs {
+  const uint8_t* data;
+  const StreamDesc* streams;
+  uint32_t nstreams;
+  const ChunkRec* rec;
+  uint64_t nrec;
+  const uint64_t* uniq;
+  const uint64_t* pack_off;
+  uint64_t nunique;
+  uint64_t total;
+  uint8_t* out;
+  DedupHdr* hdr;
+};
+hipError_t launch_pack(const PackArgs& a, bool funnel, hipStream_t s);
+
 }  // namespace bsg

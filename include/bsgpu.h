@@ -235,6 +235,66 @@ const bsg_tree_node* bsg_engine_tree_nodes_device(const bsg_engine* eng);
 const uint8_t* bsg_engine_tree_arena_device(const bsg_engine* eng);
 const uint8_t* bsg_engine_roots_device(const bsg_engine* eng);
 
+/* ---- which chunks of a run are new: Store.Put's `added`, decided on the device ---- */
+/* A store keeps one blob per ref (store/mem/mem.go:62-77 drops a blob it has and returns
+ * added = false). A bsg_refset is that knowledge kept in device memory across runs: a set of
+ * 32-byte refs that only grows. A store seeds it once from ListRefs with bsg_refset_add and then
+ * passes it to every bsg_engine_dedup. BSG_ENODEV (NULL) for a device that does not exist. */
+typedef struct bsg_refset bsg_refset;
+bsg_refset* bsg_refset_new(int device, int* err);
+void bsg_refset_free(bsg_refset* s);
+/* Refs in the set (0 for NULL). */
+uint64_t bsg_refset_count(const bsg_refset* s);
+/* Adds n refs (host memory, 32 bytes each). added (n bytes, or NULL): added[i] = 1 iff ref i was
+ * not in the set and is not an earlier entry of this call. Synchronous. The set grows by
+ * doubling, rehashed on the device, before an insert would pass its load limit; a failed
+ * allocation returns BSG_ENOMEM and leaves the set unchanged. After a device error the set is
+ * unusable: this call and every later one on it return BSG_ESTATE. BSG_EINVAL for a null set,
+ * or null refs with n > 0.
+ * Threading: a set carries its own mutex; engines on several threads may share one set, their
+ * calls on it (this one, bsg_engine_dedup with the set) serialize. */
+int bsg_refset_add(bsg_refset* s, const uint8_t* refs /* host, n x 32 */, uint64_t n,
+                   uint8_t* added /* host, n bytes, or NULL */);
+
+/* First occurrence per ref over the records r[0 .. n) of the last finished bsg_engine_run
+ * (stream-major, as bsg_engine_chunks_device), on the device. Synchronous, on the engine's
+ * stream. It leaves in device memory, valid until the next run or the next bsg_engine_dedup on
+ * this engine:
+ *   first[i]    (n entries) the smallest j with r[j].ref == r[i].ref; bit 63 is set if the ref
+ *               was in `set` before this call. Record i is NEW iff first[i] == i, bit 63 clear.
+ *   uniq[k]     (*nunique entries) the indices of the new records, ascending.
+ *   pack_off[k] (*nunique + 1 entries) the exclusive prefix sum of the new records' len;
+ *               pack_off[*nunique] == *unique_bytes.
+ * The result is a function of the records and the set's contents alone, never of scheduling:
+ * with set == NULL two calls give identical arrays. The records, the tree buffers and the run's
+ * own state are not touched; a later bsg_engine_trees or bsg_engine_run behaves as before.
+ * With a set (on the engine's device, else BSG_EINVAL): records whose ref the set holds are not
+ * new, and the new records' refs have been added to the set when the call returns, so a second
+ * call on the same run with the same set reports *nunique == 0 (every first[i] carries bit 63).
+ * BSG_EINVAL for null eng, nunique or unique_bytes; BSG_ESTATE unless the engine's last enqueue
+ * was a bsg_engine_run that bsg_engine_finish completed successfully (as bsg_engine_trees), or
+ * if the set has seen a device error; BSG_ENOMEM with the set unchanged if it cannot grow. */
+int bsg_engine_dedup(bsg_engine* eng, bsg_refset* set /* or NULL */, uint64_t* nunique,
+                     uint64_t* unique_bytes);
+/* The result to host memory: up to cap_first entries of first, up to cap_uniq of uniq and (the
+ * same number + 1) of pack_off. Any of the three pointers may be NULL. BSG_ESTATE without a
+ * dedup result for the current run (as the device pointers below are NULL). */
+int bsg_engine_copy_dedup(bsg_engine* eng, uint64_t* first, uint64_t cap_first, uint64_t* uniq,
+                          uint64_t* pack_off, uint64_t cap_uniq);
+const uint64_t* bsg_engine_dedup_first_device(const bsg_engine* eng);
+const uint64_t* bsg_engine_dedup_uniq_device(const bsg_engine* eng);
+const uint64_t* bsg_engine_dedup_pack_off_device(const bsg_engine* eng);
+/* Gathers the new records' bytes, tightly packed, into device memory:
+ *   d_out[pack_off[k] .. pack_off[k + 1]) = the bytes of record uniq[k]
+ *                                         = d_data[off[stream] + offset .. + len) of the run.
+ * One D2H copy of unique_bytes plus uniq and pack_off then gives a store all it must Put.
+ * Synchronous. The caller keeps the run's input bytes (d_data of bsg_engine_run) valid and
+ * unchanged until the call returns. No byte outside [d_out, d_out + unique_bytes) is written.
+ * BSG_ESTATE without a dedup result for the current run; BSG_EINVAL for a d_out that is null or
+ * not a multiple of 16, for cap < unique_bytes, or when [d_out, d_out + unique_bytes) intersects
+ * the run's data span (d_data up to the end of its last stream). */
+int bsg_engine_pack_unique(bsg_engine* eng, uint8_t* d_out, uint64_t cap);
+
 /* Per-stage HIP event timing of later runs, and the last finished run's stage durations in
  * ms: [0] rolling scan (k_scan), [1] prefix/compact/select/chunks, [2] SHA-256 (k_sha, and the
  * early chains' tail). Timed on the engine's own stream. enable: 0 off, 1 every stage (four
