@@ -162,6 +162,8 @@ def lib() -> ctypes.CDLL:
         "bsg_engine_diag": (ctypes.c_int, [vp, u64p]),
         "bsg_engine_timeline": (ctypes.c_int, [vp, u64p]),
         "bsg_engine_tiers_debug": (ctypes.c_int, [vp, u64p]),
+        "bsg_engine_early_min_debug": (ctypes.c_int, [vp, ctypes.c_uint64]),
+        "bsg_engine_early_picks_debug": (ctypes.c_int, [vp, u64p]),
         "bsg_engine_rescan_debug": (ctypes.c_uint64, [vp]),
         "bsg_engine_regions_debug": (ctypes.c_int, [vp, vp, ctypes.c_uint64]),
         "bsg_engine_stage_ms": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_float)]),
@@ -641,6 +643,33 @@ class Engine:
                "bsg_engine_tiers_debug")
         return {"nlong_grp": int(d[0]), "tickets_grp": int(d[1]), "helped": int(d[2]),
                 "wave_tickets": int(d[3]), "early": (bool(d[4]), bool(d[5]))}
+
+    def set_early_min(self, nbytes: int) -> None:
+        """bsg_engine_early_min_debug (test tooling, not in bsgpu.h): this engine's later runs
+        take early chains from `nbytes` on (256 MiB by default; 0: every run). KNOB_EARLY and
+        KNOB_LIGHT_BYTES apply as before."""
+        _check(lib().bsg_engine_early_min_debug(self.h, int(nbytes)),
+               "bsg_engine_early_min_debug")
+
+    def early_picks(self) -> list:
+        """bsg_engine_early_picks_debug (test tooling, not in bsgpu.h): the last finished run's
+        early chains, per filled slot (blocks, cand_index, record_index or None): k_pick's key,
+        (blocks << 32) | index of the chunk's start candidate in the sorted candidate list, and
+        the index k_lens matched it to in the run's records. Empty slots are left out (slot 1 is
+        never filled without slot 0); [] after a hash run or a run without early chains."""
+        d = np.zeros(4, dtype=np.uint64)
+        _check(lib().bsg_engine_early_picks_debug(self.h, _p(d, ctypes.c_uint64)),
+               "bsg_engine_early_picks_debug")
+        out = []
+        for k in range(2):
+            top, idx = int(d[k]), int(d[2 + k])
+            if top:
+                out.append((top >> 32, top & 0xFFFFFFFF, idx - 1 if idx else None))
+            elif idx:
+                raise BsgError(-5, f"bsg_engine_early_picks_debug: idx[{k}] without top[{k}]")
+        if not d[0] and d[1]:
+            raise BsgError(-5, "bsg_engine_early_picks_debug: top[1] without top[0]")
+        return out
 
     def regions(self) -> dict:
         """bsg_engine_regions_debug (test tooling, not in bsgpu.h): the address regions of the

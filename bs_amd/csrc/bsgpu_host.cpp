@@ -2902,6 +2902,37 @@ extern "C" int bsg_engine_tiers_debug(bsg_engine* e, uint64_t out[6]) {
   return BSG_OK;
 }
 
+// Test tooling (not in include/bsgpu.h): the run size from which this engine's later runs take
+// early chains (bsg_engine::early_min; kEarlyMinBytes by default, 0: every run). Nothing else
+// changes: BSG_KNOB_EARLY, BSG_KNOB_LIGHT_BYTES, the snapshot and hash-mode gates hold as before.
+// With it a planted run of a few hundred KiB goes through k_pick, k_early and k_early_fix.
+extern "C" int bsg_engine_early_min_debug(bsg_engine* e, uint64_t bytes) {
+  if (!e || e->enqueued) return BSG_EINVAL;
+  e->early_min = bytes;
+  return BSG_OK;
+}
+
+// Test tooling (not in include/bsgpu.h): what k_pick and k_lens left in the last finished run's
+// Early record: out[0], out[1] = Early::top[0..1] ((blocks << 32) | candidate index, 0: no
+// pick), out[2], out[3] = Early::idx[0..1] (1 + the picked chunk's record index, 0: not
+// matched). Zeros after a hash run or a run without early chains (k_start clears the record of
+// every split run, and only k_pick writes top).
+extern "C" int bsg_engine_early_picks_debug(bsg_engine* e, uint64_t out[4]) {
+  if (!e || !out || e->enqueued) return BSG_EINVAL;
+  for (int k = 0; k < 2 * kEarly; ++k) out[k] = 0;
+  if (e->hash_mode || !e->ctr.p || e->ctr.cap < sizeof(Counters) + sizeof(Early)) return BSG_OK;
+  if (e->setdev()) return BSG_EDEVICE;
+  Early ea;
+  if (hipStreamSynchronize(e->stream) != hipSuccess) return BSG_EDEVICE;
+  if (hipMemcpy(&ea, e->dearly(), sizeof(Early), hipMemcpyDeviceToHost) != hipSuccess)
+    return BSG_EDEVICE;
+  for (int k = 0; k < kEarly; ++k) {
+    out[k] = ea.top[k];
+    out[kEarly + k] = ea.idx[k];
+  }
+  return BSG_OK;
+}
+
 // Test tooling (not in include/bsgpu.h): Counters::rescan of the last finished run, the strips
 // whose candidates outnumbered their kSlotCap slots and went through k_rescan; ~0 while a run is
 // in flight or without an engine.

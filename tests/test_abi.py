@@ -111,3 +111,8 @@ def test_debug_knobs_and_null_handles():
     assert L.bsg_engine_profile(None, 2) == -22          # modes 0, 1, 2 on a real engine
     st = (ctypes.c_float * 3)()
     assert L.bsg_engine_stage_ms(None, st) == -22
+    # test tooling outside include/bsgpu.h: the early chains' threshold and picks
+    assert L.bsg_engine_early_min_debug(None, 0) == -22
+    assert L.bsg_engine_early_picks_debug(None, out.ctypes.data_as(
+        ctypes.POINTER(ctypes.c_uint64))) == -22
+    assert "bsg_engine_early_min_debug" not in bsgpu.exported_symbols_from_header()
