@@ -27,8 +27,9 @@ ERRORS = {-22: "EINVAL", -12: "ENOMEM", -5: "EDEVICE", -71: "ESTATE", -19: "ENOD
 
 
 class BsgError(RuntimeError):
-    def __init__(self, code: int, what: str = ""):
+    def __init__(self, code: int, what: str = "", info: dict | None = None):
         self.code = code
+        self.info = info  # Engine.restore: the bsg_restore_info of the failed call
         super().__init__(f"{what}: bsgpu error {code} ({ERRORS.get(code, '?')})")
 
 
@@ -79,6 +80,26 @@ TREE_NODE_DTYPE = np.dtype(
      ("reserved", "<u4"), ("ref", "u1", (32,))]
 )
 assert TREE_NODE_DTYPE.itemsize == 56
+
+# bsg_pool_blob: one blob of the pool that Engine.restore reads (pool[off : off + len], named ref)
+POOL_BLOB_DTYPE = np.dtype([("off", "<u8"), ("len", "<u8"), ("ref", "u1", (32,))])
+assert POOL_BLOB_DTYPE.itemsize == 48
+RESTORE_VERIFY = 1     # BSG_RESTORE_VERIFY
+RESTORE_TILE = 32768   # kRestoreTile: output bytes of one stream per scatter workgroup
+NONE64 = (1 << 64) - 1
+
+
+class RestoreInfo(ctypes.Structure):
+    """bsg_restore_info (include/bsgpu.h)."""
+    _fields_ = [("bad_record", ctypes.c_uint64), ("bad_blob", ctypes.c_uint64),
+                ("bytes", ctypes.c_uint64), ("verified", ctypes.c_uint64)]
+
+    def as_dict(self) -> dict:
+        return {"bad_record": int(self.bad_record), "bad_blob": int(self.bad_blob),
+                "bytes": int(self.bytes), "verified": int(self.verified)}
+
+
+assert ctypes.sizeof(RestoreInfo) == 32
 
 _lib = None
 
@@ -154,6 +175,11 @@ def lib() -> ctypes.CDLL:
         "bsg_engine_dedup_pack_off_device": (vp, [vp]),
         "bsg_engine_pack_unique": (ctypes.c_int, [vp, vp, ctypes.c_uint64]),
         "bsg_engine_dedup_ms_debug": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_float)]),
+        "bsg_engine_restore": (ctypes.c_int, [vp, vp, ctypes.c_uint64, vp, ctypes.c_uint64, vp,
+                                              ctypes.c_uint64, vp, ctypes.c_uint64, u64p, u64p,
+                                              ctypes.c_uint32, ctypes.c_int,
+                                              ctypes.POINTER(RestoreInfo)]),
+        "bsg_engine_restore_ms_debug": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_float)]),
         "bsg_engine_pack_mode_debug": (ctypes.c_int, [vp, ctypes.c_int]),
         "bsg_engine_d2d_ms_debug": (ctypes.c_int, [vp, vp, vp, ctypes.c_uint64,
                                                    ctypes.POINTER(ctypes.c_float)]),
@@ -590,6 +616,35 @@ class Engine:
         cap = buf.nbytes - offset if cap is None else cap
         _check(lib().bsg_engine_pack_unique(self.h, buf.ptr + offset, cap),
                "bsg_engine_pack_unique")
+
+    def restore(self, pool, blobs, recs, out, out_off, out_len, verify: bool = False,
+                pool_bytes: int | None = None, out_cap: int | None = None) -> dict:
+        """bsg_engine_restore: the streams that `recs` (CHUNK_DTYPE) describe, written to device
+        memory from the pool's blobs (POOL_BLOB_DTYPE): stream s to out + out_off[s]. pool / out:
+        a DeviceBuffer or a device address (then pool_bytes / out_cap must be given). Returns the
+        call's bsg_restore_info as a dict; raises BsgError (code, info) on any failure."""
+        pp = pool.ptr if isinstance(pool, DeviceBuffer) else pool
+        op = out.ptr if isinstance(out, DeviceBuffer) else out
+        pool_bytes = pool.nbytes + READ_SLACK if pool_bytes is None else pool_bytes
+        out_cap = out.nbytes if out_cap is None else out_cap
+        blobs = np.ascontiguousarray(blobs, dtype=POOL_BLOB_DTYPE)
+        recs = np.ascontiguousarray(recs, dtype=CHUNK_DTYPE)
+        oo, ol = _u64(out_off), _u64(out_len)
+        assert len(oo) == len(ol)
+        info = RestoreInfo()
+        rc = lib().bsg_engine_restore(self.h, pp, pool_bytes, blobs.ctypes.data, len(blobs),
+                                      recs.ctypes.data, len(recs), op, out_cap,
+                                      _p(oo, ctypes.c_uint64), _p(ol, ctypes.c_uint64), len(oo),
+                                      RESTORE_VERIFY if verify else 0, ctypes.byref(info))
+        if rc != BSG_OK:
+            raise BsgError(rc, "bsg_engine_restore", info.as_dict())
+        return info.as_dict()
+
+    def restore_ms(self) -> dict:
+        """The last restore() call's passes in ms (test tooling; needs profile() on)."""
+        out = (ctypes.c_float * 3)()
+        _check(lib().bsg_engine_restore_ms_debug(self.h, out), "bsg_engine_restore_ms_debug")
+        return {"resolve": float(out[0]), "verify": float(out[1]), "scatter": float(out[2])}
 
     def dedup_ms(self) -> dict:
         """The last dedup() and pack_unique() calls in ms (test tooling; needs profile() on)."""

@@ -657,6 +657,14 @@ struct bsg_engine {
   hipEvent_t dd_ev[4] = {nullptr, nullptr, nullptr, nullptr};  // profile: dedup, pack
   float dd_ms[2] = {0, 0};
 
+  // bsg_engine_restore: streams written out from a pool of blobs. The call owns every buffer
+  // here (and hashes the pool through `hasher`), so the last run's records, dedup result and
+  // tree stay as they are.
+  DevBuf r_in, r_tab, r_seg, r_runs, r_descs;
+  PinBuf h_rin, h_rhdr;
+  hipEvent_t rs_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // profile
+  float rs_ms[3] = {0, 0, 0};  // profile: index + resolve + tiling, verify, scatter
+
   // Round 5: a lightly loaded run (at most BSG_KNOB_LIGHT_BYTES, default 4 GiB, where the
   // longest chunk's chain is the step: configs[1], [3], [4]) keeps its early chains on the
   // engine stream right after k_pick and moves selection and k_sha to the second stream, so the
@@ -1141,6 +1149,19 @@ struct bsg_engine {
     return tev[i];
   }
 
+  // the second engine, in hash mode on this engine's stream (bsg_engine_trees' node blobs,
+  // bsg_engine_restore's pool blobs)
+  int need_hasher() {
+    if (hasher) return BSG_OK;
+    hasher = new (std::nothrow) bsg_engine();
+    if (!hasher) return BSG_ENOMEM;
+    hasher->dev = dev;
+    hasher->num_cus = num_cus;
+    hasher->stream = stream;
+    hasher->borrowed_stream = true;
+    return BSG_OK;
+  }
+
   int trees() {
     if (!run_done || snapshot || hash_mode) return BSG_ESTATE;
     int rc;
@@ -1192,14 +1213,7 @@ struct bsg_engine {
       HCHECK(hipMemsetAsync(t_arena.p, 0, tp.arena + kReadSlack, stream));
       if (prof) tree_event(nev++);
 
-      if (!hasher) {
-        hasher = new (std::nothrow) bsg_engine();
-        if (!hasher) return BSG_ENOMEM;
-        hasher->dev = dev;
-        hasher->num_cus = num_cus;
-        hasher->stream = stream;
-        hasher->borrowed_stream = true;
-      }
+      if ((rc = need_hasher())) return rc;
       // height by height: emit the blobs, hash them, refs into the listed records (where the
       // next height's emit reads them)
       TreeArgs ta = tree_args(tp);
@@ -1340,6 +1354,180 @@ struct bsg_engine {
     int rc;
     if ((rc = dd.readback(stream))) return rc;
     dd_elapsed(1);
+    return BSG_OK;
+  }
+
+  void rs_mark(int i) {
+    if (!profile) return;
+    if (!rs_ev[i] && hipEventCreate(&rs_ev[i]) != hipSuccess) {
+      (void)hipGetLastError();
+      rs_ev[i] = nullptr;
+    }
+    if (rs_ev[i]) (void)hipEventRecord(rs_ev[i], stream);
+  }
+  float rs_elapsed(int i, int j) {
+    float v = 0.f;
+    if (!profile || !rs_ev[i] || !rs_ev[j] ||
+        hipEventElapsedTime(&v, rs_ev[i], rs_ev[j]) != hipSuccess) {
+      (void)hipGetLastError();
+      return 0.f;
+    }
+    return v;
+  }
+
+  // the header to the host after everything enqueued on the stream
+  int restore_readback(RestoreHdr* h) {
+    HCHECK(hipMemcpyAsync(h_rhdr.p, r_in.p, sizeof(RestoreHdr), hipMemcpyDeviceToHost, stream));
+    HCHECK(stream_wait(stream));
+    *h = *h_rhdr.as<RestoreHdr>();
+    if (h->dd.error) {
+      std::fprintf(stderr, "bsgpu: restore sanity check failed (code %llu)\n",
+                   (unsigned long long)h->dd.error);
+      return BSG_EDEVICE;
+    }
+    return BSG_OK;
+  }
+
+  // bsg_engine_restore. The host checks what it can from its own arrays (pointers, alignment,
+  // the output ranges, the blobs' bounds); the records, in their hundreds of thousands, are
+  // resolved and checked on the device. Nothing is written to d_out before the header has come
+  // back clean.
+  int restore(const uint8_t* d_pool, uint64_t pool_bytes, const bsg_pool_blob* blobs,
+              uint64_t nblobs, const bsg_chunk* recs, uint64_t nrecs, uint8_t* d_out,
+              uint64_t out_cap, const uint64_t* out_off, const uint64_t* out_len, uint32_t ns,
+              int flags, bsg_restore_info* info) {
+    const bool verify = (flags & BSG_RESTORE_VERIFY) != 0;
+    if (flags & ~BSG_RESTORE_VERIFY) return BSG_EINVAL;
+    if ((!d_pool && pool_bytes) || (!blobs && nblobs) || (!recs && nrecs) || (!d_out && out_cap) ||
+        (ns && (!out_off || !out_len)))
+      return BSG_EINVAL;
+    if (reinterpret_cast<uintptr_t>(d_out) % 16 != 0) return BSG_EINVAL;
+    const uintptr_t p0 = reinterpret_cast<uintptr_t>(d_pool), p1 = p0 + pool_bytes;
+    const uintptr_t ob = reinterpret_cast<uintptr_t>(d_out);
+    if (p1 < p0 || ob + out_cap < ob) return BSG_EINVAL;
+
+    // the input block: header | blobs | records | out_off | out_len | tile prefix
+    auto pad16 = [](uint64_t v) { return (v + 15) & ~15ull; };
+    const uint64_t o_blobs = sizeof(RestoreHdr);
+    const uint64_t o_recs = o_blobs + pad16(sizeof(PoolBlob) * nblobs);
+    const uint64_t o_off = o_recs + pad16(sizeof(ChunkRec) * nrecs);
+    const uint64_t o_len = o_off + pad16(8ull * ns);
+    const uint64_t o_tpre = o_len + pad16(8ull * ns);
+    const uint64_t in_bytes = o_tpre + pad16(8ull * (ns + 1ull));
+    MCHECK(h_rin.ensure(in_bytes));
+    MCHECK(h_rhdr.ensure(sizeof(RestoreHdr)));
+    uint8_t* hin = h_rin.as<uint8_t>();
+    uint64_t* tpre = reinterpret_cast<uint64_t*>(hin + o_tpre);
+
+    uint64_t total = 0, tiles = 0;
+    std::vector<std::pair<uint64_t, uint64_t>> spans;  // the non-empty output ranges
+    for (uint32_t s = 0; s < ns; ++s) {
+      if (out_off[s] % 16 != 0 || out_off[s] > out_cap || out_len[s] > out_cap - out_off[s])
+        return BSG_EINVAL;
+      tpre[s] = tiles;
+      if (!out_len[s]) continue;
+      const uintptr_t o0 = ob + out_off[s], o1 = o0 + out_len[s];
+      if (pool_bytes && o0 < p1 && p0 < o1) return BSG_EINVAL;  // the output inside the pool
+      spans.emplace_back(out_off[s], out_off[s] + out_len[s]);
+      total += out_len[s];
+      tiles += (out_len[s] + kRestoreTile - 1) / kRestoreTile;
+    }
+    tpre[ns] = tiles;
+    std::sort(spans.begin(), spans.end());
+    for (size_t k = 1; k < spans.size(); ++k)
+      if (spans[k].first < spans[k - 1].second) return BSG_EINVAL;
+    if (tiles > 0x7fffffffull) return BSG_EINVAL;
+
+    uint64_t blob_bytes = 0, blob_hi = 0;
+    for (uint64_t k = 0; k < nblobs; ++k) {
+      if (blobs[k].off > pool_bytes || blobs[k].len > pool_bytes - blobs[k].off) return BSG_EINVAL;
+      if (verify && (blobs[k].off % 16 != 0 || blobs[k].len >= (1ull << 40))) return BSG_EINVAL;
+      blob_bytes += blobs[k].len;
+      blob_hi = std::max<uint64_t>(blob_hi, blobs[k].off + blobs[k].len);
+    }
+    // the engine hash path's own rules (bsg_engine_hash)
+    if (verify && nblobs && (p0 % 16 != 0 || pool_bytes - blob_hi < kReadSlack)) return BSG_EINVAL;
+
+    RestoreHdr* h0 = reinterpret_cast<RestoreHdr*>(hin);
+    *h0 = RestoreHdr{};
+    h0->missing = h0->mismatch = h0->bad_blob = ~0ull;
+    if (nblobs) std::memcpy(hin + o_blobs, blobs, sizeof(PoolBlob) * nblobs);
+    if (nrecs) std::memcpy(hin + o_recs, recs, sizeof(ChunkRec) * nrecs);
+    if (ns) {
+      std::memcpy(hin + o_off, out_off, 8ull * ns);
+      std::memcpy(hin + o_len, out_len, 8ull * ns);
+    }
+
+    const uint64_t slots = pow2_at_least(std::max<uint64_t>(64, 2 * nblobs));
+    const uint64_t ns1 = ns ? ns : 1;
+    MCHECK(r_in.ensure(in_bytes));
+    MCHECK(r_tab.ensure(8 * slots));
+    MCHECK(r_seg.ensure(8 * (nrecs ? nrecs : 1)));
+    MCHECK(r_runs.ensure(16 * ns1));
+    RestoreArgs a{};
+    a.pool = d_pool;
+    a.pool_bytes = pool_bytes;
+    a.blobs = reinterpret_cast<const PoolBlob*>(r_in.as<uint8_t>() + o_blobs);
+    a.nblobs = nblobs;
+    a.rec = reinterpret_cast<const ChunkRec*>(r_in.as<uint8_t>() + o_recs);
+    a.nrec = nrecs;
+    a.out_off = reinterpret_cast<const uint64_t*>(r_in.as<uint8_t>() + o_off);
+    a.out_len = reinterpret_cast<const uint64_t*>(r_in.as<uint8_t>() + o_len);
+    a.tpre = reinterpret_cast<const uint64_t*>(r_in.as<uint8_t>() + o_tpre);
+    a.ns = ns;
+    a.tab = r_tab.as<uint64_t>();
+    a.tab_mask = slots - 1;
+    a.seg = r_seg.as<uint64_t>();
+    a.sfirst = r_runs.as<uint64_t>();
+    a.slast = r_runs.as<uint64_t>() + ns1;
+    a.out = d_out;
+    a.hdr = r_in.as<RestoreHdr>();
+
+    int rc;
+    rs_mark(0);
+    HCHECK(hipMemcpyAsync(r_in.p, hin, in_bytes, hipMemcpyHostToDevice, stream));
+    HCHECK(hipMemsetAsync(r_tab.p, 0xFF, 8 * slots, stream));
+    HCHECK(hipMemsetAsync(r_runs.p, 0xFF, 16 * ns1, stream));
+    HCHECK(dbg("launch_restore_resolve", stream, launch_restore_resolve(a, stream, num_cus)));
+    rs_mark(1);
+    if (verify && nblobs) {
+      if ((rc = need_hasher())) return rc;
+      for (uint64_t b = 0; b < nblobs; b += kTreeHashBatch) {
+        const uint32_t nb = (uint32_t)std::min<uint64_t>(kTreeHashBatch, nblobs - b);
+        HCHECK(r_descs.ensure(sizeof(StreamDesc) * nb));
+        HCHECK(launch_restore_descs(a, b, nb, r_descs.as<StreamDesc>(), stream, num_cus));
+        if ((rc = hasher->enqueue_hash_device(d_pool, blob_hi, r_descs.as<StreamDesc>(), nb,
+                                              long_mode())))
+          return rc;
+        HCHECK(launch_restore_compare(a, b, nb, hasher->out.as<ChunkRec>(), hasher->dctr(),
+                                      stream, num_cus));
+      }
+    }
+    rs_mark(2);
+    RestoreHdr h;
+    if ((rc = restore_readback(&h))) return rc;
+    rs_ms[0] = rs_elapsed(0, 1);
+    rs_ms[1] = rs_elapsed(1, 2);
+    rs_ms[2] = 0.f;
+    if (h.invalid) return BSG_EINVAL;
+    if (info && verify) {
+      info->verified = blob_bytes;
+      info->bad_blob = h.bad_blob;
+    }
+    if (h.missing != ~0ull) {
+      if (info) info->bad_record = h.missing;
+      return BSG_ENOTFOUND;
+    }
+    if (info) info->bad_record = h.mismatch;
+    if (h.mismatch != ~0ull || (verify && h.bad_blob != ~0ull)) return BSG_ECORRUPT;
+    if (enqueued) return BSG_ESTATE;
+
+    rs_mark(3);
+    HCHECK(dbg("launch_restore_scatter", stream, launch_restore_scatter(a, tiles, stream)));
+    rs_mark(4);
+    if ((rc = restore_readback(&h))) return rc;
+    rs_ms[2] = rs_elapsed(3, 4);
+    if (info) info->bytes = total;
     return BSG_OK;
   }
 };
@@ -2480,6 +2668,12 @@ void bsg_engine_destroy(bsg_engine* e) {
   e->dd.release();
   for (hipEvent_t ev : e->dd_ev)
     if (ev) hipEventDestroy(ev);
+  DevBuf* rbufs[] = {&e->r_in, &e->r_tab, &e->r_seg, &e->r_runs, &e->r_descs};
+  for (DevBuf* b : rbufs) b->release();
+  e->h_rin.release();
+  e->h_rhdr.release();
+  for (hipEvent_t ev : e->rs_ev)
+    if (ev) hipEventDestroy(ev);
   for (hipEvent_t ev : e->tev)
     if (ev) hipEventDestroy(ev);
   // a failed run may have left early chains (k_pick / k_early on estream) that the engine
@@ -2704,6 +2898,31 @@ int bsg_engine_pack_unique(bsg_engine* e, uint8_t* d_out, uint64_t cap) {
   int rc = e->setdev();
   if (rc) return rc;
   return e->pack_unique(d_out, cap);
+}
+
+static_assert(sizeof(bsg_pool_blob) == sizeof(PoolBlob), "bsg_pool_blob layout");
+static_assert(sizeof(bsg_restore_info) == 32, "bsg_restore_info layout");
+
+int bsg_engine_restore(bsg_engine* e, const uint8_t* d_pool, uint64_t pool_bytes,
+                       const bsg_pool_blob* blobs, uint64_t nblobs, const bsg_chunk* recs,
+                       uint64_t nrecs, uint8_t* d_out, uint64_t out_cap, const uint64_t* out_off,
+                       const uint64_t* out_len, uint32_t nstreams, int flags,
+                       bsg_restore_info* info) {
+  if (info) *info = bsg_restore_info{UINT64_MAX, UINT64_MAX, 0, 0};
+  if (!e) return BSG_EINVAL;
+  int rc = e->setdev();
+  if (rc) return rc;
+  return e->restore(d_pool, pool_bytes, blobs, nblobs, recs, nrecs, d_out, out_cap, out_off,
+                    out_len, nstreams, flags, info);
+}
+
+// Test and measurement tooling (not in bsgpu.h): the last bsg_engine_restore call's passes in
+// ms (index + resolve + tiling check, verify, scatter), with bsg_engine_profile on.
+extern "C" int bsg_engine_restore_ms_debug(const bsg_engine* e, float out[3]) {
+  if (!e || !out) return BSG_EINVAL;
+  if (!e->profile) return BSG_ESTATE;
+  for (int i = 0; i < 3; ++i) out[i] = e->rs_ms[i];
+  return BSG_OK;
 }
 
 // Test and measurement tooling (not in bsgpu.h): the last bsg_engine_dedup and

@@ -221,4 +221,21 @@ struct DedupHdr {              // totals of one dedup pass, read back by the hos
   uint64_t pad_;
 };
 
+// Streams restored from a pool of blobs (bsg_engine_restore; bsgpu_restore.inc).
+constexpr uint32_t kRestoreTile = 32768;      // output bytes of one stream per scatter workgroup
+struct PoolBlob {              // == bsg_pool_blob (include/bsgpu.h)
+  uint64_t off;
+  uint64_t len;
+  uint8_t ref[32];
+};
+static_assert(sizeof(PoolBlob) == 48, "PoolBlob layout");
+struct RestoreHdr {            // one call's verdicts, read back by the host
+  DedupHdr dd;                 // dd.error: a device-side bound check failed (bug guard)
+  uint64_t invalid;            // the records break a layout rule (BSG_EINVAL)
+  uint64_t missing;            // smallest record whose ref the pool lacks, else ~0
+  uint64_t mismatch;           // smallest record whose len is not its blob's, else ~0
+  uint64_t bad_blob;           // smallest pool blob that does not hash to its ref, else ~0
+};
+static_assert(sizeof(RestoreHdr) == 64, "RestoreHdr layout");
+
 }  // namespace bsg

@@ -258,4 +258,37 @@ struct PackArgs {
 };
 hipError_t launch_pack(const PackArgs& a, bool funnel, hipStream_t s);
 
+// bsg_engine_restore (bsgpu_restore.inc): records name pool blobs by ref; every stream's bytes
+// are written to out + out_off[stream]. blobs .. tpre are one upload; tab, seg, sfirst and slast
+// belong to the call (tab, sfirst and slast 0xFF-filled, hdr initialised by the caller).
+struct RestoreArgs {
+  const uint8_t* pool;
+  uint64_t pool_bytes;
+  const PoolBlob* blobs;
+  uint64_t nblobs;
+  const ChunkRec* rec;
+  uint64_t nrec;
+  const uint64_t* out_off;   // [ns]
+  const uint64_t* out_len;   // [ns]
+  const uint64_t* tpre;      // [ns + 1] exclusive prefix of the streams' output tiles
+  uint32_t ns;
+  uint64_t* tab;             // [tab_mask + 1] blob indices by ref
+  uint64_t tab_mask;
+  uint64_t* seg;             // [nrec] pool offset of each record's blob
+  uint64_t* sfirst;          // [ns] a stream's first record (~0: none)
+  uint64_t* slast;           // [ns] and its last
+  uint8_t* out;
+  RestoreHdr* hdr;
+};
+// the index of the pool's refs, every record resolved against it, the records' tiling checked
+hipError_t launch_restore_resolve(const RestoreArgs& a, hipStream_t s, int num_cus);
+// blobs [b0, b0 + n) as the descriptors of a hash run, and that run's records against their refs
+hipError_t launch_restore_descs(const RestoreArgs& a, uint64_t b0, uint32_t n, StreamDesc* d,
+                                hipStream_t s, int num_cus);
+hipError_t launch_restore_compare(const RestoreArgs& a, uint64_t b0, uint32_t n,
+                                  const ChunkRec* hashed, const Counters* hctr, hipStream_t s,
+                                  int num_cus);
+// tiles: tpre[ns] (one workgroup per tile)
+hipError_t launch_restore_scatter(const RestoreArgs& a, uint64_t tiles, hipStream_t s);
+
 }  // namespace bsg

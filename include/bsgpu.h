@@ -295,6 +295,61 @@ const uint64_t* bsg_engine_dedup_pack_off_device(const bsg_engine* eng);
  * the run's data span (d_data up to the end of its last stream). */
 int bsg_engine_pack_unique(bsg_engine* eng, uint8_t* d_out, uint64_t cap);
 
+/* ---- streams restored on the device from a pool of blobs: split.Reader for many streams ---- */
+/* The inverse of bsg_engine_dedup + bsg_engine_pack_unique (split.Reader reads a tree's chunks
+ * one by one out of a store, split/split.go:169-303): every distinct blob lies once in a pool in
+ * device memory, records say which blob is which part of which stream, and the streams are
+ * written out in device memory.
+ * Blob k is d_pool[blobs[k].off .. + blobs[k].len) and is named blobs[k].ref. If two blobs carry
+ * the same ref, the one with the smaller index is used. */
+typedef struct bsg_pool_blob {
+  uint64_t off;
+  uint64_t len;
+  uint8_t ref[32];
+} bsg_pool_blob; /* 48 bytes */
+#define BSG_RESTORE_VERIFY 1 /* hash every pool blob on the device and hold it to its ref */
+typedef struct bsg_restore_info {
+  uint64_t bad_record; /* smallest failing record index, else UINT64_MAX */
+  uint64_t bad_blob;   /* smallest pool blob index whose bytes do not hash to its ref, else
+                        * UINT64_MAX */
+  uint64_t bytes;      /* bytes written to d_out (0 on any failure) */
+  uint64_t verified;   /* pool bytes hashed */
+} bsg_restore_info;
+/* Record i (stream, offset, len, ref; level is ignored; as bsg_engine_copy_chunks gives them)
+ * says: bytes [offset, offset + len) of stream `stream` are the blob with that ref. On success
+ * d_out[out_off[s] + r.offset .. + r.len) holds that blob's bytes for every record r of stream s.
+ * Synchronous, on the engine's stream. The result is a function of the arguments alone, never of
+ * scheduling.
+ * BSG_EINVAL if a layout rule is broken: a null pointer with a non-zero count; d_out or an
+ * out_off[s] not a multiple of 16; an out_off[s] + out_len[s] that wraps or exceeds out_cap; two
+ * streams' output ranges that intersect, or one that intersects the pool; a blob that ends past
+ * pool_bytes; a record with stream >= nstreams or len == 0; records not stream-major with
+ * ascending offsets; a stream s whose records do not tile [0, out_len[s]) exactly (first offset
+ * 0, no gap, no overlap, the last one's end out_len[s]; a stream of length 0 has no records).
+ * With BSG_RESTORE_VERIFY only, the engine hash path's own rules (bsg_engine_hash): d_pool or a
+ * blobs[k].off not a multiple of 16, a blob of 2^40 bytes or more, or less than BSG_READ_SLACK
+ * readable bytes (of pool_bytes) after the last blob. Without the flag blobs may start at any
+ * byte, so the tight output of bsg_engine_pack_unique is a valid pool:
+ * blobs[k] = {pack_off[k], len, ref} of record uniq[k].
+ * Then, in this order: BSG_ENOTFOUND if a record's ref is not in the pool (bad_record: the
+ * smallest such index); BSG_ECORRUPT if a record's len is not its blob's len (bad_record) or,
+ * with the flag, a blob's SHA-256 is not its ref (bad_blob; with the flag, bad_blob and verified
+ * are filled in whenever the layout was valid); BSG_ESTATE if the engine has an enqueued,
+ * unfinished run.
+ * Every check, verification included, has finished before the first byte of d_out is written:
+ * on any failure d_out is untouched. On success no byte outside the streams' output ranges is
+ * written: the gaps between streams, and the bytes after a stream's end inside its last 16-byte
+ * vector, stay as they were. The engine's last run stays valid: its records, dedup result and
+ * tree can still be read, and a later bsg_engine_run behaves as before. */
+int bsg_engine_restore(bsg_engine* eng,
+                       const uint8_t* d_pool, uint64_t pool_bytes, /* device */
+                       const bsg_pool_blob* blobs, uint64_t nblobs, /* host */
+                       const bsg_chunk* recs, uint64_t nrecs,       /* host */
+                       uint8_t* d_out, uint64_t out_cap,            /* device */
+                       const uint64_t* out_off, const uint64_t* out_len,
+                       uint32_t nstreams,                           /* host */
+                       int flags, bsg_restore_info* info /* or NULL */);
+
 /* Per-stage HIP event timing of later runs, and the last finished run's stage durations in
  * ms: [0] rolling scan (k_scan), [1] prefix/compact/select/chunks, [2] SHA-256 (k_sha, and the
  * early chains' tail). Timed on the engine's own stream. enable: 0 off, 1 every stage (four
