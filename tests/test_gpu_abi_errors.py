@@ -167,6 +167,64 @@ def test_close_in_steps(gpu, oracle, table):
     e.free()
 
 
+def test_engine_destroy_frees_every_pass(gpu, table):
+    """bsg_engine_destroy frees what every pass of the engine allocated. One engine runs a 64 KiB
+    planted stream, builds its trees, dedups into a ref set, packs, and restores with verify (so
+    the tree, dedup and restore workspaces and the second engine all hold buffers); the device
+    pointers the ABI exposes are noted, the engine destroyed and the set freed. A second engine,
+    warmed with the same zero-length hash run beforehand so that it allocates nothing now, must
+    refuse each noted pointer as d_data (BSG_EINVAL: not a live HIP allocation; checked before
+    any launch, so the pointer is never read). A pointer it accepts was leaked."""
+    import planting as P
+    import restore_cases as RC
+    L = gpu.lib()
+    bits = 8
+    data = P.level_stream(table, bits, np.tile([0, 0, 9, 0, 1, 0, 17, 0], 128))
+    assert data.size == 64 << 10
+    src = gpu.DeviceBuffer(data.size)
+    src.from_host(data)
+    out = gpu.DeviceBuffer(data.size)
+    zero = (ctypes.c_uint64 * 1)(0)
+    zp = ctypes.cast(zero, ctypes.POINTER(ctypes.c_uint64))
+
+    def hash_at(eng, ptr):
+        return L.bsg_engine_hash(eng.h, ptr, zp, zp, 1)
+
+    probe = gpu.Engine()
+    assert hash_at(probe, src.ptr) == 0
+    probe.finish()
+
+    eng, rset = gpu.Engine(), gpu.RefSet()
+    eng.run(src.ptr, [0], [data.size], bits=bits, min_size=64)
+    assert eng.finish() == 1024
+    recs = eng.chunks()
+    roots, _, nodes, _ = eng.trees()
+    assert len(roots) == 1 and len(nodes) > 1
+    _, uniq, _ = eng.dedup(rset)
+    assert 0 < eng.nunique < len(recs) and rset.count() == eng.nunique
+    packed = gpu.DeviceBuffer(eng.unique_bytes)
+    eng.pack_unique(packed)
+    u = uniq.astype(np.int64)
+    blobs = RC.make_blobs(recs["offset"][u], recs["len"][u], recs["ref"][u])
+    info = eng.restore(src, blobs, recs, out, [0], [data.size], verify=True)
+    assert info["bytes"] == data.size and info["verified"] == eng.unique_bytes
+    assert (out.to_host() == data).all()
+
+    names = ("chunks", "tree_nodes", "tree_arena", "roots", "dedup_first", "dedup_uniq",
+             "dedup_pack_off")
+    ptrs = {n: getattr(L, f"bsg_engine_{n}_device")(eng.h) for n in names}
+    assert all(ptrs.values()), ptrs
+    eng.close()
+    rset.free()
+    for n, p in ptrs.items():
+        assert hash_at(probe, p) == -22, n             # BSG_EINVAL: freed with the engine
+    assert hash_at(probe, src.ptr) == 0                # the probe still works
+    probe.finish()
+    probe.close()
+    for b in (src, out, packed):
+        b.free()
+
+
 def test_engine_profile_modes(gpu):
     """bsg_engine_profile: 1 times every stage, 2 only the SHA-256 stage (the scan and selection
     stages read -1), 0 off (stage_ms refused); other modes are refused."""
