@@ -100,6 +100,21 @@ class RestoreInfo(ctypes.Structure):
 
 
 assert ctypes.sizeof(RestoreInfo) == 32
+WALK_MAX_DEPTH = 64    # kWalkMaxDepth: a node deeper than this (Root = 0) is refused
+
+
+class WalkInfo(ctypes.Structure):
+    """bsg_walk_info (include/bsgpu.h)."""
+    _fields_ = [("bad_stream", ctypes.c_uint64), ("nrecs", ctypes.c_uint64),
+                ("nnodes", ctypes.c_uint64), ("bytes", ctypes.c_uint64),
+                ("depth", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+    def as_dict(self) -> dict:
+        return {"bad_stream": int(self.bad_stream), "nrecs": int(self.nrecs),
+                "nnodes": int(self.nnodes), "bytes": int(self.bytes), "depth": int(self.depth)}
+
+
+assert ctypes.sizeof(WalkInfo) == 40
 
 _lib = None
 
@@ -180,6 +195,16 @@ def lib() -> ctypes.CDLL:
                                               ctypes.c_uint32, ctypes.c_int,
                                               ctypes.POINTER(RestoreInfo)]),
         "bsg_engine_restore_ms_debug": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_float)]),
+        "bsg_engine_walk": (ctypes.c_int, [vp, vp, ctypes.c_uint64, vp, ctypes.c_uint64, vp,
+                                           ctypes.c_uint32, ctypes.c_int, vp,
+                                           ctypes.POINTER(WalkInfo)]),
+        "bsg_engine_copy_walk": (ctypes.c_int, [vp, vp, ctypes.c_uint64, vp, vp,
+                                                ctypes.c_uint32]),
+        "bsg_engine_walk_records_device": (vp, [vp]),
+        "bsg_engine_restore_walk": (ctypes.c_int, [vp, vp, ctypes.c_uint64, vp, ctypes.c_uint64,
+                                                   vp, ctypes.c_uint64, u64p, ctypes.c_uint32,
+                                                   ctypes.c_int, ctypes.POINTER(RestoreInfo)]),
+        "bsg_engine_walk_ms_debug": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_float)]),
         "bsg_engine_pack_mode_debug": (ctypes.c_int, [vp, ctypes.c_int]),
         "bsg_engine_d2d_ms_debug": (ctypes.c_int, [vp, vp, vp, ctypes.c_uint64,
                                                    ctypes.POINTER(ctypes.c_float)]),
@@ -530,6 +555,7 @@ class Engine:
         if not self.h:
             raise BsgError(err.value, "bsg_engine_create")
         self.nstreams = 0
+        self._walk_ns = self._walk_nrecs = 0
 
     def run(self, d_ptr: int, off, lens, bits: int = 16, min_size: int = 1024,
             fanout: int = 8) -> None:
@@ -645,6 +671,66 @@ class Engine:
         out = (ctypes.c_float * 3)()
         _check(lib().bsg_engine_restore_ms_debug(self.h, out), "bsg_engine_restore_ms_debug")
         return {"resolve": float(out[0]), "verify": float(out[1]), "scatter": float(out[2])}
+
+    def walk(self, pool, blobs, roots, pool_bytes: int | None = None, flags: int = 0):
+        """bsg_engine_walk: every stream's size and records read out of the split trees under
+        `roots` ([ns, 32] uint8, or ns * 32 bytes), whose node and chunk blobs lie in the pool
+        (POOL_BLOB_DTYPE; a DeviceBuffer, or a device address with pool_bytes). Returns
+        (rc, info, status): the return code, the bsg_walk_info as a dict and the per-stream
+        status (int32); a negative rc is returned, not raised."""
+        pp = pool.ptr if isinstance(pool, DeviceBuffer) else pool
+        pool_bytes = pool.nbytes + READ_SLACK if pool_bytes is None else pool_bytes
+        blobs = np.ascontiguousarray(blobs, dtype=POOL_BLOB_DTYPE)
+        roots = np.ascontiguousarray(np.frombuffer(roots, dtype=np.uint8)
+                                     if isinstance(roots, (bytes, bytearray)) else roots,
+                                     dtype=np.uint8).reshape(-1)
+        assert len(roots) % 32 == 0
+        ns = len(roots) // 32
+        status = np.zeros(max(ns, 1), dtype=np.int32)
+        info = WalkInfo()
+        rc = lib().bsg_engine_walk(self.h, pp, pool_bytes, blobs.ctypes.data, len(blobs),
+                                   roots.ctypes.data, ns, flags, status.ctypes.data,
+                                   ctypes.byref(info))
+        self._walk_ns, self._walk_nrecs = ns, int(info.nrecs)
+        return rc, info.as_dict(), status[:ns]
+
+    def copy_walk(self):
+        """bsg_engine_copy_walk: (recs[CHUNK_DTYPE], sizes[ns], counts[ns]) of the last
+        successful walk(); raises BsgError (ESTATE) without one."""
+        ns, n = self._walk_ns, self._walk_nrecs
+        recs = np.zeros(max(n, 1), dtype=CHUNK_DTYPE)
+        sizes = np.zeros(max(ns, 1), dtype=np.uint64)
+        counts = np.zeros(max(ns, 1), dtype=np.uint64)
+        _check(lib().bsg_engine_copy_walk(self.h, recs.ctypes.data, n, sizes.ctypes.data,
+                                          counts.ctypes.data, ns), "bsg_engine_copy_walk")
+        return recs[:n], sizes[:ns], counts[:ns]
+
+    def walk_records_device(self) -> int:
+        """bsg_engine_walk_records_device: the records' device address (0 without a walk)."""
+        return lib().bsg_engine_walk_records_device(self.h) or 0
+
+    def restore_walk(self, pool, blobs, out, out_off, verify: bool = False,
+                     pool_bytes: int | None = None, out_cap: int | None = None):
+        """bsg_engine_restore_walk: restore() with the last successful walk's records, read on
+        the device, and its sizes as out_len. Returns (rc, info): the return code and the
+        bsg_restore_info as a dict; a negative rc is returned, not raised."""
+        pp = pool.ptr if isinstance(pool, DeviceBuffer) else pool
+        op = out.ptr if isinstance(out, DeviceBuffer) else out
+        pool_bytes = pool.nbytes + READ_SLACK if pool_bytes is None else pool_bytes
+        out_cap = out.nbytes if out_cap is None else out_cap
+        blobs = np.ascontiguousarray(blobs, dtype=POOL_BLOB_DTYPE)
+        oo = _u64(out_off)
+        info = RestoreInfo()
+        rc = lib().bsg_engine_restore_walk(self.h, pp, pool_bytes, blobs.ctypes.data, len(blobs),
+                                           op, out_cap, _p(oo, ctypes.c_uint64), len(oo),
+                                           RESTORE_VERIFY if verify else 0, ctypes.byref(info))
+        return rc, info.as_dict()
+
+    def walk_ms(self) -> dict:
+        """The last walk() call's passes in ms (test tooling; needs profile() on)."""
+        out = (ctypes.c_float * 3)()
+        _check(lib().bsg_engine_walk_ms_debug(self.h, out), "bsg_engine_walk_ms_debug")
+        return {"index": float(out[0]), "levels": float(out[1]), "placement": float(out[2])}
 
     def dedup_ms(self) -> dict:
         """The last dedup() and pack_unique() calls in ms (test tooling; needs profile() on)."""

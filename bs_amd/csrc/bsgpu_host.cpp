@@ -1,7 +1,7 @@
 // bsgpu_host.cpp — libbsgpu host side: the C ABI declared in include/bsgpu.h. What it drives
 // lives in the headers included below, one per concern: host_mem.h (buffers, streams, knobs),
-// host_engine.h (the run pipeline; it includes the passes host_tree.h, host_dedup.h and
-// host_restore.h), host_stream.h (copy pool, streaming context), host_hasher.h.
+// host_engine.h (the run pipeline; it includes the passes host_tree.h, host_dedup.h,
+// host_restore.h and host_walk.h), host_stream.h (copy pool, streaming context), host_hasher.h.
 //
 // A run = one launch sequence over a batch of stream segments (bsgpu_internal.h):
 //   k_start (descriptors in, counters zeroed) → k_scan (+ its exact pass) → prefix(strip counts) →
@@ -443,8 +443,63 @@ int bsg_engine_restore(bsg_engine* e, const uint8_t* d_pool, uint64_t pool_bytes
   if (!e) return BSG_EINVAL;
   int rc = e->setdev();
   if (rc) return rc;
-  return e->restore.run(e->view(), d_pool, pool_bytes, blobs, nblobs, recs, nrecs, d_out, out_cap,
-                        out_off, out_len, nstreams, flags, info);
+  return e->restore.run(e->view(), d_pool, pool_bytes, blobs, nblobs, recs, nrecs, nullptr, d_out,
+                        out_cap, out_off, out_len, nstreams, flags, info);
+}
+
+static_assert(sizeof(bsg_walk_info) == 40, "bsg_walk_info layout");
+
+int bsg_engine_walk(bsg_engine* e, const uint8_t* d_pool, uint64_t pool_bytes,
+                    const bsg_pool_blob* blobs, uint64_t nblobs, const uint8_t* roots,
+                    uint32_t nstreams, int flags, int32_t* status, bsg_walk_info* info) {
+  if (info) *info = bsg_walk_info{UINT64_MAX, 0, 0, 0, 0, 0};
+  if (!e) return BSG_EINVAL;
+  int rc = e->setdev();
+  if (rc) return rc;
+  return e->walk.run(e->view(), d_pool, pool_bytes, blobs, nblobs, roots, nstreams, flags, status,
+                     info);
+}
+
+int bsg_engine_copy_walk(bsg_engine* e, bsg_chunk* recs, uint64_t cap, uint64_t* sizes,
+                         uint64_t* counts, uint32_t nstreams) {
+  if (!e) return BSG_EINVAL;
+  if (!e->walk.valid) return BSG_ESTATE;
+  if (nstreams > e->walk.ns) return BSG_EINVAL;
+  int rc = e->setdev();
+  if (rc) return rc;
+  const uint64_t n = std::min<uint64_t>(cap, e->walk.nrecs);
+  if (recs && n) HCHECK(hipMemcpy(recs, e->walk.recs.p, sizeof(bsg_chunk) * n, hipMemcpyDeviceToHost));
+  if (sizes && nstreams) std::memcpy(sizes, e->walk.sizes.data(), 8ull * nstreams);
+  if (counts && nstreams) std::memcpy(counts, e->walk.counts.data(), 8ull * nstreams);
+  return BSG_OK;
+}
+
+const bsg_chunk* bsg_engine_walk_records_device(const bsg_engine* e) {
+  return e && e->walk.valid ? e->walk.recs.as<const bsg_chunk>() : nullptr;
+}
+
+int bsg_engine_restore_walk(bsg_engine* e, const uint8_t* d_pool, uint64_t pool_bytes,
+                            const bsg_pool_blob* blobs, uint64_t nblobs, uint8_t* d_out,
+                            uint64_t out_cap, const uint64_t* out_off, uint32_t nstreams,
+                            int flags, bsg_restore_info* info) {
+  if (info) *info = bsg_restore_info{UINT64_MAX, UINT64_MAX, 0, 0};
+  if (!e) return BSG_EINVAL;
+  if (!e->walk.valid) return BSG_ESTATE;
+  if (nstreams != e->walk.ns) return BSG_EINVAL;
+  int rc = e->setdev();
+  if (rc) return rc;
+  return e->restore.run(e->view(), d_pool, pool_bytes, blobs, nblobs, nullptr, e->walk.nrecs,
+                        e->walk.recs.as<ChunkRec>(), d_out, out_cap, out_off,
+                        e->walk.sizes.data(), nstreams, flags, info);
+}
+
+// Test and measurement tooling (not in bsgpu.h): the last bsg_engine_walk call's passes in ms
+// (index + Roots, levels, placement), with bsg_engine_profile on.
+extern "C" int bsg_engine_walk_ms_debug(const bsg_engine* e, float out[3]) {
+  if (!e || !out) return BSG_EINVAL;
+  if (!e->profile) return BSG_ESTATE;
+  for (int i = 0; i < 3; ++i) out[i] = e->walk.ms[i];
+  return BSG_OK;
 }
 
 // Test and measurement tooling (not in bsgpu.h): the last bsg_engine_restore call's passes in

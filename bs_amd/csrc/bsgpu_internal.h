@@ -238,4 +238,41 @@ struct RestoreHdr {            // one call's verdicts, read back by the host
 };
 static_assert(sizeof(RestoreHdr) == 64, "RestoreHdr layout");
 
+// Split trees read on the device, from Roots to records (bsg_engine_walk; bsgpu_walk.inc). Breadth
+// first: level L's frontier holds every node blob at depth L (Root = 0) of every stream, sorted by
+// (stream, offset).
+constexpr uint32_t kWalkMaxDepth = 64;        // a node deeper than this is refused
+constexpr uint32_t kWalkRuns = 12;            // entry lengths 36 and 38..47: at most 11 runs
+constexpr uint64_t kWalkDead = ~0ull;         // WalkItem::blob: no node here (empty stream, miss)
+constexpr uint32_t kWalkCorrupt = 1;          // per-stream status words, merged by atomicMax:
+constexpr uint32_t kWalkNotFound = 2;         //   not found outranks corrupt outranks 0 (ok)
+struct WalkItem {              // one frontier entry
+  uint64_t blob;               // pool blob index, or kWalkDead
+  uint64_t exp_off;            // the cover its parent gives it: the node's own offset ...
+  uint64_t exp_size;           // ... and size must equal it (0: a Root, any size)
+  uint64_t parent;             // its parent's index in the level above (a Root: its stream)
+  uint32_t stream;
+  uint32_t pad_;
+};
+static_assert(sizeof(WalkItem) == 40, "WalkItem layout");
+struct WalkNode {              // what the count pass learns of a frontier entry
+  uint64_t nchild;             // 0: dead, or the node failed
+  uint64_t offset, size;       // Node.offset / Node.size
+  uint64_t nrec;               // records below it (placement, bottom-up)
+  uint64_t rbase;              // its first record's place (placement, top-down)
+  uint32_t kind;               // 0 none, 1 nodes, 2 leaves
+  uint32_t nruns;              // its entries lie in runs of equal entry length:
+  uint64_t run_pos[kWalkRuns]; //   run r starts at this byte of the blob
+  uint64_t run_idx[kWalkRuns]; //   with this child
+  uint32_t run_len[kWalkRuns]; //   and every entry of it has this many bytes
+};
+struct WalkHdr {               // one call's verdicts and per-level totals, read back by the host
+  DedupHdr dd;                 // dd.error: a device-side bound check failed (bug guard)
+  uint64_t nnodes;             // node blobs visited
+  uint64_t depth;              // deepest node visited
+  uint64_t lvl_all[kWalkMaxDepth + 1];    // children of level L's nodes
+  uint64_t lvl_nodes[kWalkMaxDepth + 1];  // ... of which `nodes` children (the next frontier)
+};
+static_assert(sizeof(WalkHdr) % 16 == 0, "WalkHdr layout");
+
 }  // namespace bsg

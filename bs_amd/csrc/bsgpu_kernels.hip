@@ -2613,5 +2613,6 @@ hipError_t launch_sha_blobs(const BlobShaArgs& a, hipStream_t s, int num_cus) {
 #include "bsgpu_tree.inc"
 #include "bsgpu_dedup.inc"
 #include "bsgpu_restore.inc"
+#include "bsgpu_walk.inc"
 
 }  // namespace bsg

@@ -291,4 +291,50 @@ hipError_t launch_restore_compare(const RestoreArgs& a, uint64_t b0, uint32_t n,
 // tiles: tpre[ns] (one workgroup per tile)
 hipError_t launch_restore_scatter(const RestoreArgs& a, uint64_t tiles, hipStream_t s);
 
+// bsg_engine_walk (bsgpu_walk.inc): from one Root per stream down a pool's node blobs to the
+// streams' sizes and records. pool .. status describe the call; level .. nnext the level a pass
+// works on; the rest the placement passes. Everything but the pool belongs to the call.
+struct WalkArgs {
+  const uint8_t* pool;
+  uint64_t pool_bytes;
+  const PoolBlob* blobs;
+  uint64_t nblobs;
+  const uint8_t* roots;      // [ns * 32]
+  uint32_t ns;
+  uint64_t* tab;             // [tab_mask + 1] blob indices by ref
+  uint64_t tab_mask;
+  WalkHdr* hdr;
+  uint64_t* sizes;           // [ns] the Root node's size, zeroed per call
+  uint32_t* status;          // [ns] kWalkCorrupt / kWalkNotFound, zeroed per call
+  uint32_t level;
+  uint32_t last;             // 1: the level's `nodes` children would be deeper than kWalkMaxDepth
+  uint64_t n;                // the level's frontier entries
+  WalkItem* items;           // [n]
+  WalkNode* nodes;           // [n]
+  uint64_t* call;            // [n + 1] exclusive prefix of the nodes' children
+  uint64_t* cnode;           // [n + 1] ... of their `nodes` children: places in the next frontier
+  uint64_t* prec;            // [n + 1] ... of the records below them
+  uint64_t nchild;           // k_wk_emit: the level's children; k_wk_records: its `leaves` children
+  WalkItem* next;            // [nnext] the next level's frontier
+  uint64_t nnext;
+  const uint64_t* down_prec; // [down_n + 1] prec of the level below (null: none)
+  uint64_t down_n;
+  const WalkNode* up_nodes;  // [up_n] the level above
+  const uint64_t* up_cnode;
+  uint64_t up_n;
+  uint64_t* part;            // [tree_scan_parts(n)] workgroup sums of a prefix pass
+  ChunkRec* rec;             // [nrec] the result
+  uint64_t nrec;
+};
+hipError_t launch_walk_index(const WalkArgs& a, hipStream_t s, int num_cus);
+hipError_t launch_walk_roots(const WalkArgs& a, hipStream_t s, int num_cus);
+// validate and count the level's nodes, then call and cnode
+hipError_t launch_walk_count(const WalkArgs& a, hipStream_t s, int num_cus);
+// one thread per child: the next frontier, the leaves held to their covers
+hipError_t launch_walk_emit(const WalkArgs& a, hipStream_t s, int num_cus);
+// placement: the records below each node (bottom-up), then each node's first record and the
+// level's records (top-down)
+hipError_t launch_walk_nrec(const WalkArgs& a, hipStream_t s, int num_cus);
+hipError_t launch_walk_place(const WalkArgs& a, hipStream_t s, int num_cus);
+
 }  // namespace bsg

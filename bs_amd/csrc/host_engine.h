@@ -53,7 +53,7 @@ uint64_t data_span(const std::vector<StreamDesc>& descs) {
   return hi;
 }
 
-// What a pass over a finished run (trees, dedup and pack, restore) takes from its engine: where
+// What a pass over a finished run (trees, dedup and pack, restore, walk) takes from its engine: where
 // it works, the run's inputs and results; `owner` only to hand on to need_hasher / hash_batches.
 struct RunView {
   bsg_engine* owner;
@@ -85,6 +85,7 @@ int hash_batches(bsg_engine* owner, DevBuf& dbuf, uint64_t n, const uint8_t* dat
 #include "host_tree.h"
 #include "host_dedup.h"
 #include "host_restore.h"
+#include "host_walk.h"
 
 struct bsg_engine {
   int dev = 0;
@@ -135,6 +136,7 @@ struct bsg_engine {
   TreeWork tree;
   DedupWork dd;
   RestoreWork restore;
+  WalkWork walk;
   RunView view() {
     return RunView{this, stream, num_cus, profile, run_done, run_done && !snapshot && !hash_mode,
                    enqueued, d_data, &descs, streams.as<StreamDesc>(), nstreams,

@@ -19,16 +19,18 @@ struct RestoreWork {
   // The host checks what it can from its own arrays (pointers, alignment, the output ranges,
   // the blobs' bounds); the records, in their hundreds of thousands, are resolved and checked
   // on the device. Nothing is written to d_out before the header has come back clean.
+  // The records come from the host (recs, uploaded with the rest) or, with d_recs, are read where
+  // they lie on the device (bsg_engine_restore_walk).
   int run(const RunView& v, const uint8_t* d_pool, uint64_t pool_bytes,
           const bsg_pool_blob* blobs, uint64_t nblobs, const bsg_chunk* recs, uint64_t nrecs,
-          uint8_t* d_out, uint64_t out_cap, const uint64_t* out_off, const uint64_t* out_len,
+          const ChunkRec* d_recs, uint8_t* d_out, uint64_t out_cap, const uint64_t* out_off, const uint64_t* out_len,
           uint32_t ns, int flags, bsg_restore_info* info) {
     const hipStream_t stream = v.stream;
     auto mark = [&](size_t i) { v.profile ? marks.record(i, stream) : void(); };
     auto elapsed = [&](size_t i, size_t j) { return v.profile ? marks.ms(i, j) : 0.f; };
     const bool verify = (flags & BSG_RESTORE_VERIFY) != 0;
     if (flags & ~BSG_RESTORE_VERIFY) return BSG_EINVAL;
-    if ((!d_pool && pool_bytes) || (!blobs && nblobs) || (!recs && nrecs) || (!d_out && out_cap) ||
+    if ((!d_pool && pool_bytes) || (!blobs && nblobs) || (!recs && !d_recs && nrecs) || (!d_out && out_cap) ||
         (ns && (!out_off || !out_len)))
       return BSG_EINVAL;
     if (reinterpret_cast<uintptr_t>(d_out) % 16 != 0) return BSG_EINVAL;
@@ -40,7 +42,7 @@ struct RestoreWork {
     auto pad16 = [](uint64_t v) { return (v + 15) & ~15ull; };
     const uint64_t o_blobs = sizeof(RestoreHdr);
     const uint64_t o_recs = o_blobs + pad16(sizeof(PoolBlob) * nblobs);
-    const uint64_t o_off = o_recs + pad16(sizeof(ChunkRec) * nrecs);
+    const uint64_t o_off = o_recs + (d_recs ? 0 : pad16(sizeof(ChunkRec) * nrecs));
     const uint64_t o_len = o_off + pad16(8ull * ns);
     const uint64_t o_tpre = o_len + pad16(8ull * ns);
     const uint64_t in_bytes = o_tpre + pad16(8ull * (ns + 1ull));
@@ -82,7 +84,7 @@ struct RestoreWork {
     *h0 = RestoreHdr{};
     h0->missing = h0->mismatch = h0->bad_blob = ~0ull;
     if (nblobs) std::memcpy(hin + o_blobs, blobs, sizeof(PoolBlob) * nblobs);
-    if (nrecs) std::memcpy(hin + o_recs, recs, sizeof(ChunkRec) * nrecs);
+    if (nrecs && !d_recs) std::memcpy(hin + o_recs, recs, sizeof(ChunkRec) * nrecs);
     if (ns) {
       std::memcpy(hin + o_off, out_off, 8ull * ns);
       std::memcpy(hin + o_len, out_len, 8ull * ns);
@@ -99,7 +101,7 @@ struct RestoreWork {
     a.pool_bytes = pool_bytes;
     a.blobs = reinterpret_cast<const PoolBlob*>(in.as<uint8_t>() + o_blobs);
     a.nblobs = nblobs;
-    a.rec = reinterpret_cast<const ChunkRec*>(in.as<uint8_t>() + o_recs);
+    a.rec = d_recs ? d_recs : reinterpret_cast<const ChunkRec*>(in.as<uint8_t>() + o_recs);
     a.nrec = nrecs;
     a.out_off = reinterpret_cast<const uint64_t*>(in.as<uint8_t>() + o_off);
     a.out_len = reinterpret_cast<const uint64_t*>(in.as<uint8_t>() + o_len);

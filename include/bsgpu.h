@@ -350,6 +350,73 @@ int bsg_engine_restore(bsg_engine* eng,
                        uint32_t nstreams,                           /* host */
                        int flags, bsg_restore_info* info /* or NULL */);
 
+/* ---- split trees read on the device, from Roots to records: split.NewReader for many streams ---- */
+/* The inverse of bsg_engine_trees (split.NewReader reads a Root's Node and follows `nodes` down
+ * to the `leaves`, split/split.go:181-303; the reachable set is split.Protect's,
+ * split/split.go:306-322). The pool holds node blobs and chunk blobs side by side (nothing marks
+ * which is which) and means what it means for bsg_engine_restore: blobs may start at any byte, of
+ * two blobs under one ref the one with the smaller index is used, refs are trusted labels and
+ * nothing is hashed here (bsg_engine_restore_walk with BSG_RESTORE_VERIFY hashes every pool blob,
+ * nodes included, before a byte is written). roots[32 * s ..) is stream s's Root; 32 zero bytes
+ * (bs.Zero, as bsg_engine_copy_roots gives for an empty stream) is an empty stream: size 0, no
+ * node, no record, status BSG_OK. Any other Root must be in the pool.
+ * A node blob is accepted only if its bytes are exactly what PutProto emits for its decoded
+ * fields (`nodes` entries, then `leaves` entries, then offset if non-zero, then size if non-zero;
+ * every ref 32 bytes; a Child's offset omitted when 0; minimal varints; no other field); it has
+ * children of one kind only, and at least one; the first child's offset equals the node's offset
+ * and the children's offsets strictly ascend; size > 0 and offset + size does not wrap; a Root's
+ * offset is 0. Child i covers the bytes from its offset to the next child's offset (the last one
+ * to the node's offset + size), and must meet its cover: a `nodes` child is a blob whose own
+ * offset and size equal the cover, a `leaves` child a blob whose len in the blob table is the
+ * cover's length (never 0). A node's `nodes` children at depth 64 (Root = 0) are refused unread,
+ * which is what ends a cycle in an unverified pool. Leaf nodes need not all lie at one depth.
+ * The walk visits every node whose parent passed its own checks, so what it visits is a function
+ * of the arguments alone. status[s] is BSG_ENOTFOUND if stream s's Root, or a child ref of a
+ * visited node that passed its checks, is not in the pool; else BSG_ECORRUPT if a visited node
+ * or a child's cover breaks a rule above; else BSG_OK.
+ * Returns, in this order: BSG_EINVAL, before anything is enqueued, for a null pointer with a
+ * non-zero count, a blob that ends past pool_bytes, flags != 0 or nstreams > 65,535;
+ * BSG_ENOTFOUND if any stream's status is that; BSG_ECORRUPT if any stream's status is that;
+ * BSG_ESTATE if the engine has an enqueued, unfinished run; BSG_ENOMEM if the result cannot be
+ * allocated. status and info's bad_stream, nnodes and depth are filled whenever the layout was
+ * valid. Synchronous, on the engine's stream.
+ * On success the engine keeps, until its next bsg_engine_walk: the records on the device
+ * (stream-major, ascending offset; stream, offset, len and ref filled, level 0) and, per stream,
+ * its size (the Root node's) and its record count. A walk that fails publishes nothing. The
+ * engine's last run, dedup result, tree and restore buffers are not touched, and an engine needs
+ * no run before it walks. */
+typedef struct bsg_walk_info {
+  uint64_t bad_stream; /* smallest stream index whose status is not BSG_OK, else UINT64_MAX */
+  uint64_t nrecs;      /* records produced (0 on any failure) */
+  uint64_t nnodes;     /* node blobs visited, over all streams (filled whenever the layout was valid) */
+  uint64_t bytes;      /* sum of the streams' sizes (0 on any failure) */
+  uint32_t depth;      /* deepest node visited, Root = 0 (0 if no node was visited) */
+  uint32_t reserved;
+} bsg_walk_info;
+int bsg_engine_walk(bsg_engine* eng,
+                    const uint8_t* d_pool, uint64_t pool_bytes,   /* device */
+                    const bsg_pool_blob* blobs, uint64_t nblobs,  /* host */
+                    const uint8_t* roots, uint32_t nstreams,      /* host, nstreams x 32 */
+                    int flags,                                    /* must be 0 */
+                    int32_t* status,                              /* host, nstreams, or NULL */
+                    bsg_walk_info* info);                         /* or NULL */
+/* The last successful walk's records (up to cap), sizes and counts (the first nstreams streams;
+ * more than the walk's is BSG_EINVAL) to host memory. Any pointer may be NULL. BSG_ESTATE without
+ * a successful walk (as the device pointer below is NULL). */
+int bsg_engine_copy_walk(bsg_engine* eng, bsg_chunk* recs, uint64_t cap,
+                         uint64_t* sizes, uint64_t* counts, uint32_t nstreams);
+const bsg_chunk* bsg_engine_walk_records_device(const bsg_engine* eng);
+/* bsg_engine_restore with recs = the last successful walk's records, read where they lie on the
+ * device, and out_len = the walk's sizes: every rule, check, order of errors, flag and
+ * bsg_restore_info field is bsg_engine_restore's. The caller reads the sizes, chooses out_off and
+ * calls it; the records never cross the host link. BSG_ESTATE without a walk, BSG_EINVAL if
+ * nstreams is not the walk's. */
+int bsg_engine_restore_walk(bsg_engine* eng,
+                            const uint8_t* d_pool, uint64_t pool_bytes,
+                            const bsg_pool_blob* blobs, uint64_t nblobs,
+                            uint8_t* d_out, uint64_t out_cap, const uint64_t* out_off,
+                            uint32_t nstreams, int flags, bsg_restore_info* info);
+
 /* Per-stage HIP event timing of later runs, and the last finished run's stage durations in
  * ms: [0] rolling scan (k_scan), [1] prefix/compact/select/chunks, [2] SHA-256 (k_sha, and the
  * early chains' tail). Timed on the engine's own stream. enable: 0 off, 1 every stage (four
