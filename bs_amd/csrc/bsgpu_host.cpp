@@ -602,13 +602,12 @@ int bsg_refset_add(bsg_refset* s, const uint8_t* refs, uint64_t n, uint8_t* adde
   HCHECK(hipSetDevice(s->dev));
   if (!n) return BSG_OK;
   int rc;
-  uint64_t slots = 0;
-  if ((rc = s->work.reserve(n, &slots))) return rc;
+  if ((rc = s->work.reserve(n))) return rc;
   MCHECK(s->staged.ensure(32 * n));
   HCHECK(hipMemcpyAsync(s->staged.p, refs, 32 * n, hipMemcpyHostToDevice, s->stream));
   HCHECK(hipMemsetAsync(s->work.hdr.p, 0, sizeof(DedupHdr), s->stream));
-  HCHECK(hipMemsetAsync(s->work.tab.p, 0xFF, 8 * slots, s->stream));
-  DedupArgs a = s->work.args(s->staged.as<uint8_t>(), 32, nullptr, 0, n, slots);
+  HCHECK(s->work.tab.clear(s->stream));
+  DedupArgs a = s->work.args(s->staged.as<uint8_t>(), 32, nullptr, 0, n);
   s->lookup_args(&a);
   HCHECK(dbg("launch_dedup", s->stream, launch_dedup(a, s->stream, s->num_cus)));
   if ((rc = s->work.readback(s->stream))) {

@@ -2610,6 +2610,7 @@ hipError_t launch_sha_blobs(const BlobShaArgs& a, hipStream_t s, int num_cus) {
   return hipGetLastError();
 }
 
+#include "bsgpu_engine_common.inc"
 #include "bsgpu_tree.inc"
 #include "bsgpu_dedup.inc"
 #include "bsgpu_restore.inc"

@@ -159,6 +159,14 @@ hipError_t launch_copy_out(const void* src, void* dst, uint64_t bytes, hipStream
 hipError_t launch_fill_splitmix(uint8_t* p, uint64_t n, uint64_t seed, hipStream_t s,
                                 int num_cus);
 
+// What the engine's passes share (bsgpu_engine_common.inc). sum_parts: the u64s of `part` a
+// prefix sum over n items needs. launch_ref_index: the blobs of a pool into a table of blob
+// indices by ref (kDedupEmpty-filled, mask + 1 >= 2 * nblobs slots); a ref's slot ends at its
+// smallest index.
+uint64_t sum_parts(uint64_t n);
+hipError_t launch_ref_index(const PoolBlob* blobs, uint64_t nblobs, uint64_t* tab, uint64_t mask,
+                            DedupHdr* hdr, hipStream_t s, int num_cus);
+
 // bsg_engine_trees (bsgpu_tree.inc): the records of a finished run in, the listed nodes, their
 // blobs and the Roots out. Every buffer but rec / scount belongs to the tree work.
 struct TreeArgs {
@@ -182,13 +190,12 @@ struct TreeArgs {
   uint64_t* pc;             // [M + 1] prefix of the leaf entries' bytes
   uint64_t* pn;             // [nn + 1] prefix of the node entries' bytes
   uint64_t* aoff;           // [nn + 1] arena offsets
-  uint64_t* part;           // [tree_scan_parts(n)] workgroup sums of a prefix pass
+  uint64_t* part;           // [sum_parts(n)] workgroup sums of a prefix pass
   uint8_t* arena;
   TreeNode* nodes;          // [nn] listed order
   uint8_t* roots;           // [ns * 32]
   uint64_t* ncount;         // [ns] listed nodes per stream
 };
-uint64_t tree_scan_parts(uint64_t n);
 hipError_t launch_tree_count(const TreeArgs& a, hipStream_t s, int num_cus);
 hipError_t launch_tree_layout(TreeArgs a, hipStream_t s, int num_cus);
 hipError_t launch_tree_emit(const TreeArgs& a, uint64_t children, hipStream_t s, int num_cus);
@@ -219,7 +226,7 @@ struct DedupArgs {
   uint64_t* bpre;            // [n + 1] exclusive prefix of the new items' lengths
   uint64_t* uniq;            // [nunique] the new items, ascending
   uint64_t* pack_off;        // [nunique + 1] exclusive prefix of their lengths
-  uint64_t* part;            // [tree_scan_parts(n)] workgroup sums of a prefix pass
+  uint64_t* part;            // [sum_parts(n)] workgroup sums of a prefix pass
   DedupHdr* hdr;
 };
 hipError_t launch_dedup(const DedupArgs& a, hipStream_t s, int num_cus);
@@ -322,11 +329,10 @@ struct WalkArgs {
   const WalkNode* up_nodes;  // [up_n] the level above
   const uint64_t* up_cnode;
   uint64_t up_n;
-  uint64_t* part;            // [tree_scan_parts(n)] workgroup sums of a prefix pass
+  uint64_t* part;            // [sum_parts(n)] workgroup sums of a prefix pass
   ChunkRec* rec;             // [nrec] the result
   uint64_t nrec;
 };
-hipError_t launch_walk_index(const WalkArgs& a, hipStream_t s, int num_cus);
 hipError_t launch_walk_roots(const WalkArgs& a, hipStream_t s, int num_cus);
 // validate and count the level's nodes, then call and cnode
 hipError_t launch_walk_count(const WalkArgs& a, hipStream_t s, int num_cus);

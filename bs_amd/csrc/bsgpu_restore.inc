@@ -1,8 +1,9 @@
 // bsgpu_restore.inc — split.Reader for many streams at once, on the device (bsg_engine_restore):
 // the inverse of bsg_engine_dedup + bsg_engine_pack_unique. A pool holds every distinct blob
 // once; records (stream, offset, len, ref) say which blob lies where; the streams are written
-// out in place. Included from bsgpu_kernels.hip after bsgpu_dedup.inc (whose table, binary
-// search and 16-byte load it uses), inside namespace bsg. DESIGN §4.9.
+// out in place. Included from bsgpu_kernels.hip, inside namespace bsg. From
+// bsgpu_engine_common.inc it takes the pool's index (launch_ref_index, pool_lookup), ref_eq,
+// seg_find and, for k_rs_scatter, gather_tile. DESIGN §4.9.
 //
 // Nothing is written to the output before every check has passed: index, resolve, the tiling
 // check and (optionally) the pool's SHA-256 verification only fill the call's own buffers and
@@ -20,23 +21,8 @@ __device__ __forceinline__ void rs_lower(uint64_t* w, uint64_t v) {
 __global__ __launch_bounds__(256) void k_rs_resolve(RestoreArgs a) {
   const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
   for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.nrec; i += stride) {
-    const uint64_t* r = reinterpret_cast<const uint64_t*>(a.rec[i].ref);
-    const uint64_t h = r[0];
-    uint64_t f = kDedupEmpty;
-    bool ended = a.nblobs == 0;
-    for (uint64_t p = 0; p <= a.tab_mask && !ended; ++p) {
-      const uint64_t cur = a.tab[(h + p) & a.tab_mask];
-      if (cur == kDedupEmpty) {
-        ended = true;
-      } else if (cur >= a.nblobs) {
-        rs_error(a.hdr, 2);
-        ended = true;
-      } else if (dd_eq(r, reinterpret_cast<const uint64_t*>(a.blobs[cur].ref))) {
-        f = cur;
-        ended = true;
-      }
-    }
-    if (!ended) rs_error(a.hdr, 1);  // the table is at most half full
+    const uint64_t f = pool_lookup(a.blobs, a.nblobs, a.tab, a.tab_mask,
+                                   reinterpret_cast<const uint64_t*>(a.rec[i].ref), &a.hdr->dd);
     uint64_t so = 0;
     if (f == kDedupEmpty) {
       rs_lower(&a.hdr->missing, i);
@@ -128,39 +114,26 @@ __global__ __launch_bounds__(256) void k_rs_compare(RestoreArgs a, uint64_t b0, 
   for (uint32_t b = blockIdx.x * blockDim.x + threadIdx.x; b < n; b += gridDim.x * blockDim.x) {
     const PoolBlob* pb = a.blobs + b0 + b;
     if (hashed[b].len != pb->len) rs_error(a.hdr, 32);
-    if (!dd_eq(reinterpret_cast<const uint64_t*>(hashed[b].ref),
-               reinterpret_cast<const uint64_t*>(pb->ref)))
+    if (!ref_eq(reinterpret_cast<const uint64_t*>(hashed[b].ref),
+                reinterpret_cast<const uint64_t*>(pb->ref)))
       rs_lower(&a.hdr->bad_blob, b0 + b);
   }
 }
 
 // ---- scatter -----------------------------------------------------------------------------------
 // Partitioned by output tiles of kRestoreTile bytes per stream. A workgroup finds its stream and
-// tile in the tile prefix and its first and last record by offset; a thread owns 16-byte output
-// vectors (out + out_off[s] is 16-byte aligned) and keeps its previous vector's segment, as
-// k_pack does. A vector inside one segment is one 16-byte load at whatever residue the blob
-// has; a vector across segment ends is gathered byte by byte; a stream's last partial vector is
-// stored byte by byte.
-struct RsSeg {
-  const uint8_t* src;  // the blob's first byte (null: none)
-  uint64_t b0, b1;     // its bytes of the stream
+// tile in the tile prefix and its first and last record by offset. A segment is a record: its
+// blob's bytes in the pool, its bytes of the stream (out + out_off[s] is 16-byte aligned);
+// gather_tile does the rest.
+struct RsOffset {  // seg_find's key: a record's offset in its stream
+  const ChunkRec* rec;
+  __device__ uint64_t operator()(uint64_t k) const { return rec[k].offset; }
 };
-
-// the largest k in [lo, hi) with rec[k].offset <= key (rec[lo].offset <= key)
-__device__ __forceinline__ uint64_t rs_find(const ChunkRec* rec, uint64_t lo, uint64_t hi,
-                                            uint64_t key) {
-  while (hi - lo > 1) {
-    const uint64_t mid = (lo + hi) >> 1;
-    if (rec[mid].offset <= key) lo = mid;
-    else hi = mid;
-  }
-  return lo;
-}
 
 // the segment of stream s (slen bytes) that holds byte `pos`, among records [*k, k1]
 __device__ __forceinline__ bool rs_locate(const RestoreArgs& a, uint32_t s, uint64_t slen,
-                                          uint64_t* k, uint64_t k1, uint64_t pos, RsSeg* g) {
-  *k = rs_find(a.rec, *k, k1 + 1, pos);
+                                          uint64_t* k, uint64_t k1, uint64_t pos, GatherSeg* g) {
+  *k = seg_find(*k, k1 + 1, pos, RsOffset{a.rec});
   const uint64_t off = a.rec[*k].offset, len = a.rec[*k].len, so = a.seg[*k];
   g->src = nullptr;
   if (a.rec[*k].stream != s || pos < off || off > slen || len > slen - off || pos - off >= len ||
@@ -178,7 +151,7 @@ __global__ __launch_bounds__(256) void k_rs_scatter(RestoreArgs a) {
   __shared__ uint64_t sh[6];
   if (threadIdx.x == 0) {
     const uint64_t b = blockIdx.x;
-    const uint64_t s = pack_seg(a.tpre, 0, a.ns, b);
+    const uint64_t s = seg_find(0, a.ns, b, [&a](uint64_t k) { return a.tpre[k]; });
     const uint64_t slen = a.out_len[s], r0 = a.sfirst[s], r1 = a.slast[s];
     const uint64_t t0 = a.tpre[s] <= b ? (b - a.tpre[s]) * kRestoreTile : ~0ull;
     sh[0] = 0;
@@ -190,8 +163,8 @@ __global__ __launch_bounds__(256) void k_rs_scatter(RestoreArgs a) {
       sh[1] = s;
       sh[2] = t0;
       sh[3] = t1;
-      sh[4] = rs_find(a.rec, r0, r1 + 1, t0);
-      sh[5] = rs_find(a.rec, sh[4], r1 + 1, t1 - 1);
+      sh[4] = seg_find(r0, r1 + 1, t0, RsOffset{a.rec});
+      sh[5] = seg_find(sh[4], r1 + 1, t1 - 1, RsOffset{a.rec});
     }
   }
   __syncthreads();
@@ -203,71 +176,38 @@ __global__ __launch_bounds__(256) void k_rs_scatter(RestoreArgs a) {
     if (threadIdx.x == 0) rs_error(a.hdr, 64);
     return;
   }
-  uint8_t* out = a.out + oo;
   uint64_t k = sh[4];
-  RsSeg g = {nullptr, 0, 0};
-  for (uint64_t o = t0 + 16ull * threadIdx.x; o < t1; o += 16ull * 256) {
-    if ((!g.src || o >= g.b1) && !rs_locate(a, s, slen, &k, k1, o, &g)) continue;
-    if (o + 16 <= g.b1) {  // (b1 <= slen)
-      *reinterpret_cast<pk_u32x4a*>(out + o) = pack_load16<false>(g.src + (o - g.b0));
-      continue;
-    }
-    uint32_t w[4] = {0, 0, 0, 0};
-    uint32_t nb = 0;
-    bool live = true;  // (no break: the loop unrolls and w[] stays in registers)
-#pragma unroll
-    for (uint32_t b = 0; b < 16; ++b) {
-      const uint64_t ob = o + b;
-      live = live && ob < slen;
-      if (live && ob >= g.b1) live = rs_locate(a, s, slen, &k, k1, ob, &g);
-      if (live) {
-        w[b >> 2] |= (uint32_t)g.src[ob - g.b0] << (8 * (b & 3));
-        nb = b + 1;
-      }
-    }
-    if (!g.src) continue;
-    if (nb == 16) {
-      *reinterpret_cast<pk_u32x4a*>(out + o) = pk_u32x4a{w[0], w[1], w[2], w[3]};
-    } else {  // the stream's last vector: only its own bytes
-#pragma unroll
-      for (uint32_t b = 0; b < 16; ++b)
-        if (b < nb) out[o + b] = (uint8_t)(w[b >> 2] >> (8 * (b & 3)));
-    }
-  }
+  gather_tile<false>(a.out + oo, t0, t1, slen, [&](uint64_t pos, GatherSeg* g) {
+    return rs_locate(a, s, slen, &k, k1, pos, g);
+  });
 }
 
 // ---- launchers ---------------------------------------------------------------------------------
 hipError_t launch_restore_resolve(const RestoreArgs& a, hipStream_t s, int num_cus) {
-  if (a.nblobs) {  // k_dd_insert over the blobs' refs: a ref's slot ends at its smallest index
-    DedupArgs d{};
-    d.refs = reinterpret_cast<const uint8_t*>(a.blobs) + offsetof(PoolBlob, ref);
-    d.stride = sizeof(PoolBlob);
-    d.n = a.nblobs;
-    d.tab = a.tab;
-    d.tab_mask = a.tab_mask;
-    d.hdr = &a.hdr->dd;
-    hipLaunchKernelGGL(k_dd_insert, dim3(tree_grid(a.nblobs, num_cus)), dim3(256), 0, s, d);
-  }
+  const hipError_t e =
+      launch_ref_index(a.blobs, a.nblobs, a.tab, a.tab_mask, &a.hdr->dd, s, num_cus);
+  if (e != hipSuccess) return e;
   if (a.nrec) {
-    const uint32_t g = tree_grid(a.nrec, num_cus);
+    const uint32_t g = engine_grid(a.nrec, num_cus);
     hipLaunchKernelGGL(k_rs_resolve, dim3(g), dim3(256), 0, s, a);
     hipLaunchKernelGGL(k_rs_check, dim3(g), dim3(256), 0, s, a);
   }
-  if (a.ns) hipLaunchKernelGGL(k_rs_streams, dim3(tree_grid(a.ns, num_cus)), dim3(256), 0, s, a);
+  if (a.ns)
+    hipLaunchKernelGGL(k_rs_streams, dim3(engine_grid(a.ns, num_cus)), dim3(256), 0, s, a);
   return hipGetLastError();
 }
 
 hipError_t launch_restore_descs(const RestoreArgs& a, uint64_t b0, uint32_t n, StreamDesc* d,
                                 hipStream_t s, int num_cus) {
-  hipLaunchKernelGGL(k_rs_descs, dim3(tree_grid(n, num_cus)), dim3(256), 0, s, a, b0, n, d);
+  hipLaunchKernelGGL(k_rs_descs, dim3(engine_grid(n, num_cus)), dim3(256), 0, s, a, b0, n, d);
   return hipGetLastError();
 }
 
 hipError_t launch_restore_compare(const RestoreArgs& a, uint64_t b0, uint32_t n,
                                   const ChunkRec* hashed, const Counters* hctr, hipStream_t s,
                                   int num_cus) {
-  hipLaunchKernelGGL(k_rs_compare, dim3(tree_grid(n, num_cus)), dim3(256), 0, s, a, b0, n, hashed,
-                     hctr);
+  hipLaunchKernelGGL(k_rs_compare, dim3(engine_grid(n, num_cus)), dim3(256), 0, s, a, b0, n,
+                     hashed, hctr);
   return hipGetLastError();
 }
 

@@ -1,6 +1,7 @@
 // bsgpu_tree.inc — split.Writer's tree (split/split.go:51-126) for every stream of a finished
 // run, built on the device from the run's chunk records (bsg_engine_trees). Included from
-// bsgpu_kernels.hip, inside namespace bsg.
+// bsgpu_kernels.hip, inside namespace bsg. From bsgpu_engine_common.inc it takes the prefix sum
+// (launch_sum, wg_exclusive_sum) and engine_grid.
 //
 // Closed form (DESIGN §4, "Trees on the device"). With q_i = level_i / fanout, a stream's tree
 // after the single-child prune has its Root at height R = max q_i over every chunk but the last
@@ -16,7 +17,10 @@
 // position inside a blob is a difference of two prefix sums. No pass loops over a node's
 // children on one thread.
 
-constexpr uint32_t kTreeTile = 2048;  // items per workgroup of the prefix passes (256 x 8)
+// The tile of the shared prefix sum, under the name and in the file where the trees' limit tests
+// read it (tests/tree_cases.py): they put a run on each side of one tile and of 256 tiles.
+constexpr uint32_t kTreeTile = 2048;
+static_assert(kTreeTile == kSumTile, "the tree limit tests pin the prefix sum's tile");
 
 __device__ __forceinline__ void tree_error(const TreeArgs& a, uint64_t code) {
   atomicOr(reinterpret_cast<unsigned long long*>(&a.hdr->error), (unsigned long long)code);
@@ -88,73 +92,6 @@ struct TvArena {  // blobs start 16-byte aligned (the SHA-256 loaders)
   }
 };
 
-// ---- exclusive prefix sums over n host-known items: out[0 .. n], out[n] = the total ----------
-// blockDim.x == 256. Returns this thread's exclusive prefix of v within the workgroup.
-__device__ __forceinline__ uint64_t tree_block_scan(uint64_t v, uint64_t* total) {
-  __shared__ uint64_t wsum[4];
-  const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  uint64_t x = v;
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint64_t y = (uint64_t)__shfl_up((unsigned long long)x, o);
-    if (lane >= (uint32_t)o) x += y;
-  }
-  __syncthreads();  // wsum of a previous call has been read
-  if (lane == 63) wsum[w] = x;
-  __syncthreads();
-  uint64_t base = 0, tot = 0;
-  for (uint32_t k = 0; k < 4; ++k) {
-    if (k < w) base += wsum[k];
-    tot += wsum[k];
-  }
-  *total = tot;
-  return base + x - v;
-}
-
-template <class V>
-__global__ __launch_bounds__(256) void k_tree_scan_part(TreeArgs a, uint64_t n) {
-  const uint64_t i0 = (uint64_t)blockIdx.x * kTreeTile + threadIdx.x * 8ull;
-  uint64_t v = 0;
-  for (uint32_t k = 0; k < 8; ++k)
-    if (i0 + k < n) v += V()(a, i0 + k);
-  uint64_t tot;
-  (void)tree_block_scan(v, &tot);
-  if (threadIdx.x == 0) a.part[blockIdx.x] = tot;
-}
-
-// one workgroup: part[0 .. nb) -> its exclusive prefix, part[nb] = the total
-__global__ __launch_bounds__(256) void k_tree_scan_mid(uint64_t* part, uint64_t nb) {
-  const uint64_t per = (nb + 255) / 256;
-  const uint64_t b0 = threadIdx.x * per;
-  uint64_t v = 0;
-  for (uint64_t k = b0; k < b0 + per && k < nb; ++k) v += part[k];
-  uint64_t tot;
-  uint64_t run = tree_block_scan(v, &tot);
-  for (uint64_t k = b0; k < b0 + per && k < nb; ++k) {
-    const uint64_t x = part[k];
-    part[k] = run;
-    run += x;
-  }
-  if (threadIdx.x == 0) part[nb] = tot;
-}
-
-template <class V>
-__global__ __launch_bounds__(256) void k_tree_scan_final(TreeArgs a, uint64_t n, uint64_t nb,
-                                                         uint64_t* out) {
-  const uint64_t i0 = (uint64_t)blockIdx.x * kTreeTile + threadIdx.x * 8ull;
-  uint64_t x[8], v = 0;
-  for (uint32_t k = 0; k < 8; ++k) {
-    x[k] = i0 + k < n ? V()(a, i0 + k) : 0;
-    v += x[k];
-  }
-  uint64_t tot;
-  uint64_t run = a.part[blockIdx.x] + tree_block_scan(v, &tot);
-  for (uint32_t k = 0; k < 8; ++k) {
-    if (i0 + k < n) out[i0 + k] = run;
-    run += x[k];
-  }
-  if (blockIdx.x == 0 && threadIdx.x == 0) out[n] = a.part[nb];
-}
-
 // ---- counting -------------------------------------------------------------------------------
 // rmax[s] = R: the largest q over every chunk of the stream but its last (rmax starts zeroed)
 __global__ __launch_bounds__(256) void k_tree_rmax(TreeArgs a) {
@@ -208,7 +145,7 @@ __global__ __launch_bounds__(256) void k_tree_kcnt(TreeArgs a) {
     sum += k;
   }
   uint64_t tot;
-  (void)tree_block_scan(sum, &tot);
+  (void)wg_exclusive_sum(sum, &tot);
   __shared__ uint32_t smx;
   if (threadIdx.x == 0) smx = 0;
   __syncthreads();
@@ -428,31 +365,10 @@ __global__ __launch_bounds__(256) void k_tree_roots(TreeArgs a) {
 }
 
 // ---- launchers ------------------------------------------------------------------------------
-static inline uint32_t tree_grid(uint64_t items, int num_cus) {
-  uint64_t g = (items + 255) / 256;
-  const uint64_t cap = 8ull * (uint32_t)num_cus;
-  if (g < 1) g = 1;
-  return (uint32_t)(g < cap ? g : cap);
-}
-
-uint64_t tree_scan_parts(uint64_t n) {
-  const uint64_t nb = (n + kTreeTile - 1) / kTreeTile;
-  return (nb ? nb : 1) + 1;  // one per workgroup, then the total
-}
-
-template <class V>
-static hipError_t tree_scan(const TreeArgs& a, uint64_t n, uint64_t* out, hipStream_t s) {
-  const uint64_t nb = tree_scan_parts(n) - 1;
-  hipLaunchKernelGGL(k_tree_scan_part<V>, dim3((uint32_t)nb), dim3(256), 0, s, a, n);
-  hipLaunchKernelGGL(k_tree_scan_mid, dim3(1), dim3(256), 0, s, a.part, nb);
-  hipLaunchKernelGGL(k_tree_scan_final<V>, dim3((uint32_t)nb), dim3(256), 0, s, a, n, nb, out);
-  return hipGetLastError();
-}
-
 hipError_t launch_tree_count(const TreeArgs& a, hipStream_t s, int num_cus) {
-  hipError_t e = tree_scan<TvCount>(a, a.ns, a.cstart, s);
+  hipError_t e = launch_sum<TvCount>(a, a.ns, a.cstart, s);
   if (e != hipSuccess) return e;
-  const uint32_t g = tree_grid(a.M, num_cus);
+  const uint32_t g = engine_grid(a.M, num_cus);
   hipLaunchKernelGGL(k_tree_rmax, dim3(g), dim3(256), 0, s, a);
   hipLaunchKernelGGL(k_tree_kcnt, dim3(g), dim3(256), 0, s, a);
   return hipGetLastError();
@@ -461,23 +377,24 @@ hipError_t launch_tree_count(const TreeArgs& a, hipStream_t s, int num_cus) {
 hipError_t launch_tree_layout(TreeArgs a, hipStream_t s, int num_cus) {
   hipError_t e;
   for (a.h = 0; a.h < a.H; ++a.h) {
-    if ((e = tree_scan<TvCloses>(a, a.M, a.tmp, s)) != hipSuccess) return e;
-    hipLaunchKernelGGL(k_tree_compact, dim3(tree_grid(a.M, num_cus)), dim3(256), 0, s, a);
+    if ((e = launch_sum<TvCloses>(a, a.M, a.tmp, s)) != hipSuccess) return e;
+    hipLaunchKernelGGL(k_tree_compact, dim3(engine_grid(a.M, num_cus)), dim3(256), 0, s, a);
   }
   a.h = 0;
-  if ((e = tree_scan<TvStreamHeight>(a, (uint64_t)a.ns * a.H, a.shbase, s)) != hipSuccess) return e;
-  const uint32_t gn = tree_grid(a.nn, num_cus);
+  e = launch_sum<TvStreamHeight>(a, (uint64_t)a.ns * a.H, a.shbase, s);
+  if (e != hipSuccess) return e;
+  const uint32_t gn = engine_grid(a.nn, num_cus);
   hipLaunchKernelGGL(k_tree_meta, dim3(gn), dim3(256), 0, s, a);
-  if ((e = tree_scan<TvLeafEntry>(a, a.M, a.pc, s)) != hipSuccess) return e;
-  if ((e = tree_scan<TvNodeEntry>(a, a.nn, a.pn, s)) != hipSuccess) return e;
+  if ((e = launch_sum<TvLeafEntry>(a, a.M, a.pc, s)) != hipSuccess) return e;
+  if ((e = launch_sum<TvNodeEntry>(a, a.nn, a.pn, s)) != hipSuccess) return e;
   hipLaunchKernelGGL(k_tree_len, dim3(gn), dim3(256), 0, s, a);
-  if ((e = tree_scan<TvArena>(a, a.nn, a.aoff, s)) != hipSuccess) return e;
+  if ((e = launch_sum<TvArena>(a, a.nn, a.aoff, s)) != hipSuccess) return e;
   hipLaunchKernelGGL(k_tree_place, dim3(gn), dim3(256), 0, s, a);
   return hipGetLastError();
 }
 
 hipError_t launch_tree_emit(const TreeArgs& a, uint64_t children, hipStream_t s, int num_cus) {
-  const uint32_t g = tree_grid(children, num_cus);
+  const uint32_t g = engine_grid(children, num_cus);
   if (a.h == 0) hipLaunchKernelGGL(k_tree_emit_leaves, dim3(g), dim3(256), 0, s, a);
   else hipLaunchKernelGGL(k_tree_emit_nodes, dim3(g), dim3(256), 0, s, a);
   return hipGetLastError();
@@ -485,18 +402,18 @@ hipError_t launch_tree_emit(const TreeArgs& a, uint64_t children, hipStream_t s,
 
 hipError_t launch_tree_descs(const TreeArgs& a, uint64_t u0, uint32_t n, StreamDesc* d,
                              hipStream_t s, int num_cus) {
-  hipLaunchKernelGGL(k_tree_descs, dim3(tree_grid(n, num_cus)), dim3(256), 0, s, a, u0, n, d);
+  hipLaunchKernelGGL(k_tree_descs, dim3(engine_grid(n, num_cus)), dim3(256), 0, s, a, u0, n, d);
   return hipGetLastError();
 }
 
 hipError_t launch_tree_refs(const TreeArgs& a, uint64_t u0, uint32_t n, const ChunkRec* hashed,
                             const Counters* hctr, hipStream_t s, int num_cus) {
-  hipLaunchKernelGGL(k_tree_refs, dim3(tree_grid(n, num_cus)), dim3(256), 0, s, a, u0, n, hashed,
+  hipLaunchKernelGGL(k_tree_refs, dim3(engine_grid(n, num_cus)), dim3(256), 0, s, a, u0, n, hashed,
                      hctr);
   return hipGetLastError();
 }
 
 hipError_t launch_tree_roots(const TreeArgs& a, hipStream_t s, int num_cus) {
-  hipLaunchKernelGGL(k_tree_roots, dim3(tree_grid(a.ns, num_cus)), dim3(256), 0, s, a);
+  hipLaunchKernelGGL(k_tree_roots, dim3(engine_grid(a.ns, num_cus)), dim3(256), 0, s, a);
   return hipGetLastError();
 }

@@ -2,8 +2,9 @@
 // (bsg_engine_walk): the inverse of bsg_engine_trees. A pool holds node blobs and chunk blobs side
 // by side; from one Root per stream the walk follows `nodes` down to the `leaves` and leaves every
 // stream's size and its records in the form bsg_engine_restore takes. Included from
-// bsgpu_kernels.hip after bsgpu_restore.inc (whose index, probe and search it shares), inside
-// namespace bsg. DESIGN §4.10.
+// bsgpu_kernels.hip, inside namespace bsg. From bsgpu_engine_common.inc it takes the pool's index
+// (launch_ref_index on the host's side, pool_lookup here), the prefix sum (launch_sum) and
+// seg_find. DESIGN §4.10.
 //
 // Breadth first, every stream at once. Level L's frontier is every node at depth L, sorted by
 // (stream, offset). Per level: one wave per node validates the blob's bytes and counts its
@@ -34,23 +35,7 @@ __device__ __forceinline__ void wk_status(const WalkArgs& a, uint32_t s, uint32_
 
 // the smallest pool blob index named r, or kDedupEmpty
 __device__ __forceinline__ uint64_t wk_probe(const WalkArgs& a, const uint64_t* r) {
-  const uint64_t h = r[0];
-  uint64_t f = kDedupEmpty;
-  bool ended = a.nblobs == 0;
-  for (uint64_t p = 0; p <= a.tab_mask && !ended; ++p) {
-    const uint64_t cur = a.tab[(h + p) & a.tab_mask];
-    if (cur == kDedupEmpty) {
-      ended = true;
-    } else if (cur >= a.nblobs) {
-      wk_error(a, 2);
-      ended = true;
-    } else if (dd_eq(r, reinterpret_cast<const uint64_t*>(a.blobs[cur].ref))) {
-      f = cur;
-      ended = true;
-    }
-  }
-  if (!ended) wk_error(a, 1);  // the table is at most half full
-  return f;
+  return pool_lookup(a.blobs, a.nblobs, a.tab, a.tab_mask, r, &a.hdr->dd);
 }
 
 // blob k's bytes and length (null, and the error flag, if it does not lie in the pool)
@@ -219,7 +204,7 @@ __global__ __launch_bounds__(256) void k_wk_count(WalkArgs a) {
   }
 }
 
-// ---- prefix sums over a level's nodes (the tree's three-kernel form) ---------------------------
+// ---- the values the prefix passes sum over a level's nodes -------------------------------------
 struct WvAll {
   __device__ uint64_t operator()(const WalkArgs& a, uint64_t i) const { return a.nodes[i].nchild; }
 };
@@ -231,34 +216,6 @@ struct WvNodes {
 struct WvRecs {
   __device__ uint64_t operator()(const WalkArgs& a, uint64_t i) const { return a.nodes[i].nrec; }
 };
-
-template <class V>
-__global__ __launch_bounds__(256) void k_wk_scan_part(WalkArgs a) {
-  const uint64_t i0 = (uint64_t)blockIdx.x * kTreeTile + threadIdx.x * 8ull;
-  uint64_t v = 0;
-  for (uint32_t k = 0; k < 8; ++k)
-    if (i0 + k < a.n) v += V()(a, i0 + k);
-  uint64_t tot;
-  (void)tree_block_scan(v, &tot);
-  if (threadIdx.x == 0) a.part[blockIdx.x] = tot;
-}
-
-template <class V>
-__global__ __launch_bounds__(256) void k_wk_scan_final(WalkArgs a, uint64_t nb, uint64_t* out) {
-  const uint64_t i0 = (uint64_t)blockIdx.x * kTreeTile + threadIdx.x * 8ull;
-  uint64_t x[8], v = 0;
-  for (uint32_t k = 0; k < 8; ++k) {
-    x[k] = i0 + k < a.n ? V()(a, i0 + k) : 0;
-    v += x[k];
-  }
-  uint64_t tot;
-  uint64_t run = a.part[blockIdx.x] + tree_block_scan(v, &tot);
-  for (uint32_t k = 0; k < 8; ++k) {
-    if (i0 + k < a.n) out[i0 + k] = run;
-    run += x[k];
-  }
-  if (blockIdx.x == 0 && threadIdx.x == 0) out[a.n] = a.part[nb];
-}
 
 // ---- a node's child k ----------------------------------------------------------------------------
 // where entry k lies in the blob's len bytes, by the node's runs (false, and the error flag, if
@@ -321,7 +278,7 @@ __device__ __forceinline__ bool wk_child(const WalkArgs& a, uint64_t i, uint64_t
 __global__ __launch_bounds__(256) void k_wk_emit(WalkArgs a) {
   const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
   for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < a.nchild; t += stride) {
-    const uint64_t i = pack_seg(a.call, 0, a.n, t);
+    const uint64_t i = seg_find(0, a.n, t, [&a](uint64_t j) { return a.call[j]; });
     const uint64_t k = t - a.call[i];
     const uint32_t s = a.items[i].stream;
     WkChild c;
@@ -390,23 +347,12 @@ __global__ __launch_bounds__(256) void k_wk_rbase(WalkArgs a) {
   }
 }
 
-// the largest i in [0, n) whose leaf children start at or before t (call - cnode: the prefix of
-// the `leaves` children alone)
-__device__ __forceinline__ uint64_t wk_leaf_seg(const WalkArgs& a, uint64_t t) {
-  uint64_t lo = 0, hi = a.n;
-  while (hi - lo > 1) {
-    const uint64_t mid = (lo + hi) >> 1;
-    if (a.call[mid] - a.cnode[mid] <= t) lo = mid;
-    else hi = mid;
-  }
-  return lo;
-}
-
 // one thread per `leaves` child of the level: its record, at its place in stream order
 __global__ __launch_bounds__(256) void k_wk_records(WalkArgs a) {
   const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
   for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < a.nchild; t += stride) {
-    const uint64_t i = wk_leaf_seg(a, t);
+    // the node whose leaf children hold t (call - cnode: the prefix of the `leaves` children alone)
+    const uint64_t i = seg_find(0, a.n, t, [&a](uint64_t j) { return a.call[j] - a.cnode[j]; });
     const uint64_t l0 = a.call[i] - a.cnode[i];
     WkChild c;
     if (t < l0 || a.nodes[i].kind != 2 || !wk_child(a, i, t - l0, &c)) {
@@ -429,33 +375,8 @@ __global__ __launch_bounds__(256) void k_wk_records(WalkArgs a) {
 }
 
 // ---- launchers ---------------------------------------------------------------------------------
-template <class V>
-static hipError_t wk_scan(const WalkArgs& a, uint64_t* out, hipStream_t s) {
-  const uint64_t nb = tree_scan_parts(a.n) - 1;
-  hipLaunchKernelGGL(k_wk_scan_part<V>, dim3((uint32_t)nb), dim3(256), 0, s, a);
-  hipLaunchKernelGGL(k_tree_scan_mid, dim3(1), dim3(256), 0, s, a.part, nb);
-  hipLaunchKernelGGL(k_wk_scan_final<V>, dim3((uint32_t)nb), dim3(256), 0, s, a, nb, out);
-  return hipGetLastError();
-}
-
-// k_dd_insert over the blobs' refs, exactly as restore: a ref's slot ends at its smallest index
-// (a.tab is 0xFF-filled, the header, sizes and status zeroed by the caller)
-hipError_t launch_walk_index(const WalkArgs& a, hipStream_t s, int num_cus) {
-  if (a.nblobs) {
-    DedupArgs d{};
-    d.refs = reinterpret_cast<const uint8_t*>(a.blobs) + offsetof(PoolBlob, ref);
-    d.stride = sizeof(PoolBlob);
-    d.n = a.nblobs;
-    d.tab = a.tab;
-    d.tab_mask = a.tab_mask;
-    d.hdr = &a.hdr->dd;
-    hipLaunchKernelGGL(k_dd_insert, dim3(tree_grid(a.nblobs, num_cus)), dim3(256), 0, s, d);
-  }
-  return hipGetLastError();
-}
-
 hipError_t launch_walk_roots(const WalkArgs& a, hipStream_t s, int num_cus) {
-  if (a.ns) hipLaunchKernelGGL(k_wk_roots, dim3(tree_grid(a.ns, num_cus)), dim3(256), 0, s, a);
+  if (a.ns) hipLaunchKernelGGL(k_wk_roots, dim3(engine_grid(a.ns, num_cus)), dim3(256), 0, s, a);
   return hipGetLastError();
 }
 
@@ -465,25 +386,25 @@ hipError_t launch_walk_count(const WalkArgs& a, hipStream_t s, int num_cus) {
   const uint64_t g = want < cap ? want : cap;
   hipLaunchKernelGGL(k_wk_count, dim3((uint32_t)g), dim3(256), 0, s, a);
   hipError_t e;
-  if ((e = wk_scan<WvAll>(a, a.call, s)) != hipSuccess) return e;
-  return wk_scan<WvNodes>(a, a.cnode, s);
+  if ((e = launch_sum<WvAll>(a, a.n, a.call, s)) != hipSuccess) return e;
+  return launch_sum<WvNodes>(a, a.n, a.cnode, s);
 }
 
 hipError_t launch_walk_emit(const WalkArgs& a, hipStream_t s, int num_cus) {
   if (!a.nchild) return hipSuccess;
-  hipLaunchKernelGGL(k_wk_emit, dim3(tree_grid(a.nchild, num_cus)), dim3(256), 0, s, a);
+  hipLaunchKernelGGL(k_wk_emit, dim3(engine_grid(a.nchild, num_cus)), dim3(256), 0, s, a);
   return hipGetLastError();
 }
 
 hipError_t launch_walk_nrec(const WalkArgs& a, hipStream_t s, int num_cus) {
-  hipLaunchKernelGGL(k_wk_nrec, dim3(tree_grid(a.n, num_cus)), dim3(256), 0, s, a);
-  return wk_scan<WvRecs>(a, a.prec, s);
+  hipLaunchKernelGGL(k_wk_nrec, dim3(engine_grid(a.n, num_cus)), dim3(256), 0, s, a);
+  return launch_sum<WvRecs>(a, a.n, a.prec, s);
 }
 
 // a.nchild: the level's `leaves` children
 hipError_t launch_walk_place(const WalkArgs& a, hipStream_t s, int num_cus) {
-  hipLaunchKernelGGL(k_wk_rbase, dim3(tree_grid(a.n, num_cus)), dim3(256), 0, s, a);
+  hipLaunchKernelGGL(k_wk_rbase, dim3(engine_grid(a.n, num_cus)), dim3(256), 0, s, a);
   if (a.nchild)
-    hipLaunchKernelGGL(k_wk_records, dim3(tree_grid(a.nchild, num_cus)), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(k_wk_records, dim3(engine_grid(a.nchild, num_cus)), dim3(256), 0, s, a);
   return hipGetLastError();
 }

@@ -7,7 +7,8 @@ namespace {
 // The buffers of one first-occurrence pass (launch_dedup) over n items, and its results. An
 // engine owns one for bsg_engine_dedup (run / pack), a set one for bsg_refset_add (the buffers).
 struct DedupWork {
-  DevBuf tab, first, rank, bpre, uniq, pack_off, part, hdr;
+  RefTable tab;
+  DevBuf first, rank, bpre, uniq, pack_off, part, hdr;
   PinBuf h_hdr;
   DedupHdr last{};
   bool valid = false;  // run() made the result from the engine's current run
@@ -18,31 +19,30 @@ struct DedupWork {
 
   bool current(bool run_done) const { return valid && run_done; }  // (any enqueue clears valid)
 
-  int reserve(uint64_t n, uint64_t* slots) {
+  int reserve(uint64_t n) {
     const uint64_t n1 = n ? n : 1;
-    *slots = pow2_at_least(std::max<uint64_t>(64, 2 * n1));
-    MCHECK(tab.ensure(8 * *slots));
+    MCHECK(tab.reserve(n1));
     MCHECK(first.ensure(8 * n1));
     MCHECK(rank.ensure(8 * (n1 + 1)));
     MCHECK(bpre.ensure(8 * (n1 + 1)));
     MCHECK(uniq.ensure(8 * n1));
     MCHECK(pack_off.ensure(8 * (n1 + 1)));
-    MCHECK(part.ensure(8 * tree_scan_parts(n1)));
+    MCHECK(part.ensure(8 * sum_parts(n1)));
     MCHECK(hdr.ensure(sizeof(DedupHdr)));
     MCHECK(h_hdr.ensure(sizeof(DedupHdr)));
     return BSG_OK;
   }
 
   DedupArgs args(const uint8_t* refs, uint64_t stride, const uint8_t* lens, uint64_t len_stride,
-                 uint64_t n, uint64_t slots) const {
+                 uint64_t n) const {
     DedupArgs a{};
     a.refs = refs;
     a.stride = stride;
     a.lens = lens;
     a.len_stride = len_stride;
     a.n = n;
-    a.tab = tab.as<uint64_t>();
-    a.tab_mask = slots - 1;
+    a.tab = tab.p();
+    a.tab_mask = tab.mask();
     a.first = first.as<uint64_t>();
     a.rank = rank.as<uint64_t>();
     a.bpre = bpre.as<uint64_t>();
@@ -173,16 +173,15 @@ inline int DedupWork::run(const RunView& v, bsg_refset* set) {
   }
   int rc;
   const hipStream_t stream = v.stream;
-  uint64_t slots = 0;
-  if ((rc = reserve(v.nrec, &slots))) return rc;
+  if ((rc = reserve(v.nrec))) return rc;
   if (v.profile) marks.record(0, stream);
   HCHECK(hipMemsetAsync(hdr.p, 0, sizeof(DedupHdr), stream));
   const uint8_t* rec = reinterpret_cast<const uint8_t*>(v.rec);
   DedupArgs a = args(rec + offsetof(ChunkRec, ref), sizeof(ChunkRec),
-                     rec + offsetof(ChunkRec, len), sizeof(ChunkRec), v.nrec, slots);
+                     rec + offsetof(ChunkRec, len), sizeof(ChunkRec), v.nrec);
   if (set) set->lookup_args(&a);
   if (v.nrec) {
-    HCHECK(hipMemsetAsync(tab.p, 0xFF, 8 * slots, stream));
+    HCHECK(tab.clear(stream));
     HCHECK(dbg("launch_dedup", stream, launch_dedup(a, stream, v.num_cus)));
   } else {
     HCHECK(hipMemsetAsync(pack_off.p, 0, 8, stream));

@@ -1,5 +1,6 @@
 // host_mem.h — owning device / pinned buffers and events, the stream pool, DevicePool, the knobs,
-// stream_wait, HCHECK / MCHECK, and what the passes share: timed marks, a header read back.
+// stream_wait, HCHECK / MCHECK, and what the passes share: a table of refs, timed marks, a header
+// read back.
 #pragma once
 
 static int device_node(int device);  // NUMA node of a HIP device (below)
@@ -371,6 +372,20 @@ uint64_t pow2_at_least(uint64_t v) {
   while (p < v) p <<= 1;
   return p;
 }
+
+// The device table of indices by ref of one pass over n refs (bsgpu_engine_common.inc): at most
+// half full, every slot kDedupEmpty before the pass inserts.
+struct RefTable {
+  DevBuf tab;
+  uint64_t slots = 0;  // a power of two
+  hipError_t reserve(uint64_t n) {
+    slots = pow2_at_least(std::max<uint64_t>(64, 2 * n));
+    return tab.ensure(8 * slots);
+  }
+  hipError_t clear(hipStream_t s) { return hipMemsetAsync(tab.p, 0xFF, 8 * slots, s); }
+  uint64_t* p() const { return tab.as<uint64_t>(); }
+  uint64_t mask() const { return slots - 1; }
+};
 
 // One HIP event, created at first use and destroyed with its owner (move-only).
 struct Event {

@@ -6,7 +6,8 @@ namespace {
 // The call owns every buffer here (and hashes the pool through the engine's second engine), so
 // the last run's records, dedup result and tree stay as they are.
 struct RestoreWork {
-  DevBuf in, tab, seg, runs, descs;
+  DevBuf in, seg, runs, descs;
+  RefTable tab;
   PinBuf h_in, h_hdr;
   Marks marks;              // profile
   float ms[3] = {0, 0, 0};  // profile: index + resolve + tiling, verify, scatter
@@ -90,10 +91,9 @@ struct RestoreWork {
       std::memcpy(hin + o_len, out_len, 8ull * ns);
     }
 
-    const uint64_t slots = pow2_at_least(std::max<uint64_t>(64, 2 * nblobs));
     const uint64_t ns1 = ns ? ns : 1;
     MCHECK(in.ensure(in_bytes));
-    MCHECK(tab.ensure(8 * slots));
+    MCHECK(tab.reserve(nblobs));
     MCHECK(seg.ensure(8 * (nrecs ? nrecs : 1)));
     MCHECK(runs.ensure(16 * ns1));
     RestoreArgs a{};
@@ -107,8 +107,8 @@ struct RestoreWork {
     a.out_len = reinterpret_cast<const uint64_t*>(in.as<uint8_t>() + o_len);
     a.tpre = reinterpret_cast<const uint64_t*>(in.as<uint8_t>() + o_tpre);
     a.ns = ns;
-    a.tab = tab.as<uint64_t>();
-    a.tab_mask = slots - 1;
+    a.tab = tab.p();
+    a.tab_mask = tab.mask();
     a.seg = seg.as<uint64_t>();
     a.sfirst = runs.as<uint64_t>();
     a.slast = runs.as<uint64_t>() + ns1;
@@ -118,7 +118,7 @@ struct RestoreWork {
     int rc;
     mark(0);
     HCHECK(hipMemcpyAsync(in.p, hin, in_bytes, hipMemcpyHostToDevice, stream));
-    HCHECK(hipMemsetAsync(tab.p, 0xFF, 8 * slots, stream));
+    HCHECK(tab.clear(stream));
     HCHECK(hipMemsetAsync(runs.p, 0xFF, 16 * ns1, stream));
     HCHECK(dbg("launch_restore_resolve", stream, launch_restore_resolve(a, stream, v.num_cus)));
     mark(1);

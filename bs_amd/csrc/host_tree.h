@@ -82,7 +82,7 @@ struct TreeWork {
     HCHECK(kcnt.ensure(m1));
     HCHECK(tmp.ensure(8 * (m1 + 1)));
     HCHECK(pc.ensure(8 * (m1 + 1)));
-    HCHECK(part.ensure(8 * tree_scan_parts(std::max<uint64_t>(m1, nn1))));
+    HCHECK(part.ensure(8 * sum_parts(std::max<uint64_t>(m1, nn1))));
     HCHECK(roots.ensure(32 * nn1));
     HCHECK(ncount.ensure(8 * nn1));
     if (prof) marks.record(nev++, stream);
@@ -103,7 +103,7 @@ struct TreeWork {
       HCHECK(pn.ensure(8 * (tp.nn + 1)));
       HCHECK(aoff.ensure(8 * (tp.nn + 1)));
       HCHECK(nodes.ensure(sizeof(TreeNode) * tp.nn));
-      HCHECK(part.ensure(8 * tree_scan_parts(std::max<uint64_t>(
+      HCHECK(part.ensure(8 * sum_parts(std::max<uint64_t>(
                                  std::max<uint64_t>(m1, tp.nn), (uint64_t)tp.ns * tp.H))));
       HCHECK(dbg("launch_tree_layout", stream, launch_tree_layout(args(v, tp), stream, v.num_cus)));
       if ((rc = readback(stream, &h))) return rc;

@@ -16,7 +16,8 @@ struct WalkLevel {
 // buffers stay as they are. The result (records on the device, sizes and counts on the host)
 // lives until the next call.
 struct WalkWork {
-  DevBuf in, tab, part, recs;
+  DevBuf in, part, recs;
+  RefTable tab;
   std::vector<WalkLevel> lv;
   PinBuf h_in, h_out;
   std::vector<uint64_t> sizes, counts;  // per stream, of the last successful walk
@@ -60,10 +61,9 @@ struct WalkWork {
     if (nblobs) std::memcpy(hin + o_blobs, blobs, sizeof(PoolBlob) * nblobs);
     if (nstreams) std::memcpy(hin + o_roots, roots, 32ull * nstreams);
 
-    const uint64_t slots = pow2_at_least(std::max<uint64_t>(64, 2 * nblobs));
     lv.resize(kWalkMaxDepth + 2);
     MCHECK(in.ensure(in_bytes));
-    MCHECK(tab.ensure(8 * slots));
+    MCHECK(tab.reserve(nblobs));
     MCHECK(lv[0].items.ensure(sizeof(WalkItem) * nstreams));
     WalkArgs base{};
     base.pool = d_pool;
@@ -72,8 +72,8 @@ struct WalkWork {
     base.nblobs = nblobs;
     base.roots = in.as<uint8_t>() + o_roots;
     base.ns = nstreams;
-    base.tab = tab.as<uint64_t>();
-    base.tab_mask = slots - 1;
+    base.tab = tab.p();
+    base.tab_mask = tab.mask();
     base.hdr = in.as<WalkHdr>();
     base.sizes = reinterpret_cast<uint64_t*>(in.as<uint8_t>() + o_sizes);
     base.status = reinterpret_cast<uint32_t*>(in.as<uint8_t>() + o_status);
@@ -95,8 +95,10 @@ struct WalkWork {
     int rc;
     mark(0);
     HCHECK(hipMemcpyAsync(in.p, hin, in_bytes, hipMemcpyHostToDevice, stream));
-    HCHECK(hipMemsetAsync(tab.p, 0xFF, 8 * slots, stream));
-    HCHECK(dbg("launch_walk_index", stream, launch_walk_index(base, stream, v.num_cus)));
+    HCHECK(tab.clear(stream));
+    HCHECK(dbg("launch_ref_index", stream,
+               launch_ref_index(base.blobs, nblobs, base.tab, base.tab_mask, &base.hdr->dd, stream,
+                                v.num_cus)));
     {
       WalkArgs a = base;
       a.items = lv[0].items.as<WalkItem>();
@@ -115,7 +117,7 @@ struct WalkWork {
       MCHECK(l.call.ensure(8 * (n + 1)));
       MCHECK(l.cnode.ensure(8 * (n + 1)));
       MCHECK(l.prec.ensure(8 * (n + 1)));
-      MCHECK(part.ensure(8 * tree_scan_parts(n)));
+      MCHECK(part.ensure(8 * sum_parts(n)));
       WalkArgs a = level_args(L);
       HCHECK(dbg("launch_walk_count", stream, launch_walk_count(a, stream, v.num_cus)));
       if ((rc = readback(stream, &h))) return rc;

@@ -130,7 +130,7 @@ def test_limits_read_from_source():
     lim = TC.limits()
     assert lim["kTreeHashBatch"] == 65535       # bsg_engine_hash takes no more blobs
     assert lim["kTreeWaveNodes"] < lim["kTreeHashBatch"]
-    assert lim["kTreeTile"] == 256 * 8           # k_tree_scan_part: 256 threads x 8 items
+    assert lim["kTreeTile"] == 256 * 8           # k_sum_part: 256 threads x 8 items
     # levels are at most 32 (TrailingZeros32), so q <= 32 and a tree has at most 33 heights;
     # kcnt is a uint8_t
     assert 33 <= lim["kTreeMaxHeights"] - 1 and lim["kTreeMaxHeights"] <= 255

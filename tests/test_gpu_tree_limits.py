@@ -156,7 +156,7 @@ def test_scan_one_tile(gpu, oracle, table, chunks):
 @pytest.mark.parametrize("chunks", [SCAN - 1, SCAN, SCAN + 1])
 def test_scan_middle_pass_second_step(gpu, oracle, table, chunks):
     """The run's chunks fill 256 tiles of the prefix sums less one item, exactly, and one more:
-    with the 257th tile k_tree_scan_mid sums two tiles per thread. Roots, per-stream counts,
+    with the 257th tile k_sum_mid sums two tiles per thread. Roots, per-stream counts,
     the per-height histogram and the arena's gaps (32 MiB per run: not node by node)."""
     lists = TC.chunk_threshold_run(chunks, chunks, 6000)
     assert sum(len(x) for x in lists) == chunks and 0 < len(lists[0]) < SCAN - 1

@@ -27,7 +27,7 @@ def limits() -> dict:
                            re.M)
         assert len(m) == 1, (name, fn, m)
         out[name] = int(m[0])
-    out["scan_items"] = 256 * out["kTreeTile"]  # k_tree_scan_mid: 256 threads, one tile each
+    out["scan_items"] = 256 * out["kTreeTile"]  # k_sum_mid: 256 threads, one tile each
     return out
 
 
