@@ -115,6 +115,23 @@ class WalkInfo(ctypes.Structure):
 
 
 assert ctypes.sizeof(WalkInfo) == 40
+GC_MISSING_LEAVES = 1  # BSG_GC_MISSING_LEAVES (gc_mark)
+GC_ALIGN16 = 1         # BSG_GC_ALIGN16 (copy_gc, gc_compact)
+
+
+class GcInfo(ctypes.Structure):
+    """bsg_gc_info (include/bsgpu.h)."""
+    _fields_ = [("bad_root", ctypes.c_uint64), ("bad_blob", ctypes.c_uint64),
+                ("nlive", ctypes.c_uint64), ("live_bytes", ctypes.c_uint64),
+                ("ndead", ctypes.c_uint64), ("dead_bytes", ctypes.c_uint64),
+                ("nnodes", ctypes.c_uint64), ("missing_leaves", ctypes.c_uint64),
+                ("depth", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+    def as_dict(self) -> dict:
+        return {k: int(getattr(self, k)) for k, _ in self._fields_ if k != "reserved"}
+
+
+assert ctypes.sizeof(GcInfo) == 72
 
 _lib = None
 
@@ -205,6 +222,15 @@ def lib() -> ctypes.CDLL:
                                                    vp, ctypes.c_uint64, u64p, ctypes.c_uint32,
                                                    ctypes.c_int, ctypes.POINTER(RestoreInfo)]),
         "bsg_engine_walk_ms_debug": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_float)]),
+        "bsg_engine_gc_mark": (ctypes.c_int, [vp, vp, ctypes.c_uint64, vp, ctypes.c_uint64, vp,
+                                              ctypes.c_uint64, ctypes.c_int, vp,
+                                              ctypes.POINTER(GcInfo)]),
+        "bsg_engine_copy_gc": (ctypes.c_int, [vp, vp, ctypes.c_uint64, vp, ctypes.c_uint64,
+                                              ctypes.c_int]),
+        "bsg_engine_gc_live_device": (vp, [vp]),
+        "bsg_engine_gc_compact": (ctypes.c_int, [vp, vp, ctypes.c_uint64, vp, ctypes.c_uint64,
+                                                 ctypes.c_int, u64p]),
+        "bsg_engine_gc_ms_debug": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_float)]),
         "bsg_engine_pack_mode_debug": (ctypes.c_int, [vp, ctypes.c_int]),
         "bsg_engine_d2d_ms_debug": (ctypes.c_int, [vp, vp, vp, ctypes.c_uint64,
                                                    ctypes.POINTER(ctypes.c_float)]),
@@ -556,6 +582,7 @@ class Engine:
             raise BsgError(err.value, "bsg_engine_create")
         self.nstreams = 0
         self._walk_ns = self._walk_nrecs = 0
+        self._gc_nblobs = self._gc_nlive = 0
 
     def run(self, d_ptr: int, off, lens, bits: int = 16, min_size: int = 1024,
             fanout: int = 8) -> None:
@@ -731,6 +758,64 @@ class Engine:
         out = (ctypes.c_float * 3)()
         _check(lib().bsg_engine_walk_ms_debug(self.h, out), "bsg_engine_walk_ms_debug")
         return {"index": float(out[0]), "levels": float(out[1]), "placement": float(out[2])}
+
+    def gc_mark(self, pool, blobs, roots, pool_bytes: int | None = None, flags: int = 0):
+        """bsg_engine_gc_mark: which blobs of the pool (POOL_BLOB_DTYPE; a DeviceBuffer, or a
+        device address with pool_bytes) the `roots` ([n, 32] uint8, or n * 32 bytes) reach.
+        Returns (rc, info, status): the return code, the bsg_gc_info as a dict and the per-Root
+        status (int32); a negative rc is returned, not raised."""
+        pp = pool.ptr if isinstance(pool, DeviceBuffer) else pool
+        pool_bytes = pool.nbytes + READ_SLACK if pool_bytes is None else pool_bytes
+        blobs = np.ascontiguousarray(blobs, dtype=POOL_BLOB_DTYPE)
+        roots = np.ascontiguousarray(np.frombuffer(roots, dtype=np.uint8)
+                                     if isinstance(roots, (bytes, bytearray)) else roots,
+                                     dtype=np.uint8).reshape(-1)
+        assert len(roots) % 32 == 0
+        nr = len(roots) // 32
+        status = np.zeros(max(nr, 1), dtype=np.int32)
+        info = GcInfo()
+        rc = lib().bsg_engine_gc_mark(self.h, pp, pool_bytes, blobs.ctypes.data, len(blobs),
+                                      roots.ctypes.data, nr, flags, status.ctypes.data,
+                                      ctypes.byref(info))
+        self._gc_nblobs, self._gc_nlive = len(blobs), int(info.nlive)
+        return rc, info.as_dict(), status[:nr]
+
+    def copy_gc(self, align16: bool = False):
+        """bsg_engine_copy_gc: (live[nblobs] uint8, table[nlive] POOL_BLOB_DTYPE) of the last
+        successful gc_mark(), the table with the tight or the 16-aligned new offsets; raises
+        BsgError (ESTATE) without one."""
+        nb, nl = self._gc_nblobs, self._gc_nlive
+        live = np.zeros(max(nb, 1), dtype=np.uint8)
+        table = np.zeros(max(nl, 1), dtype=POOL_BLOB_DTYPE)
+        _check(lib().bsg_engine_copy_gc(self.h, live.ctypes.data, nb, table.ctypes.data, nl,
+                                        GC_ALIGN16 if align16 else 0), "bsg_engine_copy_gc")
+        return live[:nb], table[:nl]
+
+    def gc_live_device(self) -> int:
+        """bsg_engine_gc_live_device: live[]'s device address (0 without a mark)."""
+        return lib().bsg_engine_gc_live_device(self.h) or 0
+
+    def gc_compact(self, pool, out, align16: bool = False, pool_bytes: int | None = None,
+                   cap: int | None = None):
+        """bsg_engine_gc_compact: the last mark's live blobs gathered into `out` (a DeviceBuffer,
+        or a device address with cap). Returns (rc, out_bytes); a negative rc is returned, not
+        raised."""
+        pp = pool.ptr if isinstance(pool, DeviceBuffer) else pool
+        op = out.ptr if isinstance(out, DeviceBuffer) else out
+        pool_bytes = pool.nbytes + READ_SLACK if pool_bytes is None else pool_bytes
+        cap = out.nbytes if cap is None else cap
+        n = ctypes.c_uint64(0)
+        rc = lib().bsg_engine_gc_compact(self.h, pp, pool_bytes, op, cap,
+                                         GC_ALIGN16 if align16 else 0, ctypes.byref(n))
+        return rc, n.value
+
+    def gc_ms(self) -> dict:
+        """The last gc_mark() call's stages and the last gc_compact() in ms (test tooling; needs
+        profile() on)."""
+        out = (ctypes.c_float * 4)()
+        _check(lib().bsg_engine_gc_ms_debug(self.h, out), "bsg_engine_gc_ms_debug")
+        return {"index": float(out[0]), "levels": float(out[1]), "offsets": float(out[2]),
+                "compact": float(out[3])}
 
     def dedup_ms(self) -> dict:
         """The last dedup() and pack_unique() calls in ms (test tooling; needs profile() on)."""

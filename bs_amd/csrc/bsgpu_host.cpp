@@ -1,7 +1,7 @@
 // bsgpu_host.cpp — libbsgpu host side: the C ABI declared in include/bsgpu.h. What it drives
 // lives in the headers included below, one per concern: host_mem.h (buffers, streams, knobs),
 // host_engine.h (the run pipeline; it includes the passes host_tree.h, host_dedup.h,
-// host_restore.h and host_walk.h), host_stream.h (copy pool, streaming context), host_hasher.h.
+// host_restore.h, host_walk.h and host_gc.h), host_stream.h (copy pool, streaming context), host_hasher.h.
 //
 // A run = one launch sequence over a batch of stream segments (bsgpu_internal.h):
 //   k_start (descriptors in, counters zeroed) → k_scan (+ its exact pass) → prefix(strip counts) →
@@ -491,6 +491,49 @@ int bsg_engine_restore_walk(bsg_engine* e, const uint8_t* d_pool, uint64_t pool_
   return e->restore.run(e->view(), d_pool, pool_bytes, blobs, nblobs, nullptr, e->walk.nrecs,
                         e->walk.recs.as<ChunkRec>(), d_out, out_cap, out_off,
                         e->walk.sizes.data(), nstreams, flags, info);
+}
+
+static_assert(sizeof(bsg_gc_info) == 72, "bsg_gc_info layout");
+
+int bsg_engine_gc_mark(bsg_engine* e, const uint8_t* d_pool, uint64_t pool_bytes,
+                       const bsg_pool_blob* blobs, uint64_t nblobs, const uint8_t* roots,
+                       uint64_t nroots, int flags, int32_t* status, bsg_gc_info* info) {
+  if (info) *info = bsg_gc_info{UINT64_MAX, UINT64_MAX, 0, 0, 0, 0, 0, 0, 0, 0};
+  if (!e) return BSG_EINVAL;
+  int rc = e->setdev();
+  if (rc) return rc;
+  return e->gc.mark(e->view(), d_pool, pool_bytes, blobs, nblobs, roots, nroots, flags, status,
+                    info);
+}
+
+int bsg_engine_copy_gc(bsg_engine* e, uint8_t* live, uint64_t cap_live, bsg_pool_blob* table,
+                       uint64_t cap_table, int flags) {
+  if (!e) return BSG_EINVAL;
+  int rc = e->setdev();
+  if (rc) return rc;
+  return e->gc.copy(live, cap_live, table, cap_table, flags);
+}
+
+const uint8_t* bsg_engine_gc_live_device(const bsg_engine* e) {
+  return e && e->gc.valid ? e->gc.live.as<const uint8_t>() : nullptr;
+}
+
+int bsg_engine_gc_compact(bsg_engine* e, const uint8_t* d_pool, uint64_t pool_bytes,
+                          uint8_t* d_out, uint64_t cap, int flags, uint64_t* out_bytes) {
+  if (!e) return BSG_EINVAL;
+  int rc = e->setdev();
+  if (rc) return rc;
+  return e->gc.compact(e->view(), d_pool, pool_bytes, d_out, cap, flags, out_bytes);
+}
+
+// Test and measurement tooling (not in bsgpu.h): the last bsg_engine_gc_mark call's stages in ms
+// (index + Roots, levels, offsets) and the last bsg_engine_gc_compact, with bsg_engine_profile on.
+extern "C" int bsg_engine_gc_ms_debug(const bsg_engine* e, float out[4]) {
+  if (!e || !out) return BSG_EINVAL;
+  if (!e->profile) return BSG_ESTATE;
+  for (int i = 0; i < 3; ++i) out[i] = e->gc.ms[i];
+  out[3] = e->gc.compact_ms;
+  return BSG_OK;
 }
 
 // Test and measurement tooling (not in bsgpu.h): the last bsg_engine_walk call's passes in ms

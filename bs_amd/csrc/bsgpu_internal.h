@@ -6,6 +6,7 @@
 // reference split/split.go:99-126) carries a 64-byte window history, the open chunk's start
 // and its SHA-256 midstate from one segment to the next.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 
 namespace bsg {
@@ -252,8 +253,9 @@ struct WalkItem {              // one frontier entry
   uint64_t exp_size;           // ... and size must equal it (0: a Root, any size)
   uint64_t parent;             // its parent's index in the level above (a Root: its stream)
   uint32_t stream;
-  uint32_t pad_;
+  uint32_t flags;              // kWalkNoCover: held to the node's own rules only (exp_* unused)
 };
+constexpr uint32_t kWalkNoCover = 1;          // WalkItem::flags (bsg_engine_gc_mark's entries)
 static_assert(sizeof(WalkItem) == 40, "WalkItem layout");
 struct WalkNode {              // what the count pass learns of a frontier entry
   uint64_t nchild;             // 0: dead, or the node failed
@@ -274,5 +276,27 @@ struct WalkHdr {               // one call's verdicts and per-level totals, read
   uint64_t lvl_nodes[kWalkMaxDepth + 1];  // ... of which `nodes` children (the next frontier)
 };
 static_assert(sizeof(WalkHdr) % 16 == 0, "WalkHdr layout");
+
+// A pool garbage-collected on the device from its Roots (bsg_engine_gc_mark / _compact;
+// bsgpu_gc.inc). The mark is the walk's breadth-first search without covers and with every blob
+// expanded once: level L's frontier holds the node blobs whose nearest Root is L edges away.
+constexpr uint32_t kGcClaimed = 1;            // GcArgs::state[k]: blob k has a frontier entry
+constexpr uint32_t kGcFailed = 2;             //   ... and failed the node rules
+constexpr uint32_t kGcTile = 32768;           // output bytes per workgroup of the compaction
+struct GcHdr {                 // one mark's verdicts and totals, read back by the host
+  WalkHdr w;                   // the count pass's header (w.dd.error: the bug guard)
+  uint64_t bad_form;           // smallest blob index of a node that fails its rules, else ~0
+  uint64_t bad_miss;           // smallest blob index of a node that names a child the pool lacks
+  uint64_t verdict;            // kWalkCorrupt / kWalkNotFound, merged by atomicMax
+  uint64_t leaf_miss;          // a forgiven `leaves` miss was seen (BSG_GC_MISSING_LEAVES)
+  uint64_t missing_leaves;     // distinct such refs (k_gc_missing)
+  uint64_t end, end16;         // the end of the last live blob's bytes, tight and 16-aligned
+  uint64_t size0;              // what the count pass writes for its one stream (unused)
+  uint32_t status0;            // (unused)
+  uint32_t pad_;
+  uint64_t pad2_;
+  uint8_t zero[16];            // the bytes of ALIGN16's padding
+};
+static_assert(sizeof(GcHdr) % 16 == 0 && offsetof(GcHdr, zero) % 16 == 0, "GcHdr layout");
 
 }  // namespace bsg

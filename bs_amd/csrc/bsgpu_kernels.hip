@@ -2615,5 +2615,6 @@ hipError_t launch_sha_blobs(const BlobShaArgs& a, hipStream_t s, int num_cus) {
 #include "bsgpu_dedup.inc"
 #include "bsgpu_restore.inc"
 #include "bsgpu_walk.inc"
+#include "bsgpu_gc.inc"
 
 }  // namespace bsg

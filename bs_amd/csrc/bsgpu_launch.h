@@ -343,4 +343,37 @@ hipError_t launch_walk_emit(const WalkArgs& a, hipStream_t s, int num_cus);
 hipError_t launch_walk_nrec(const WalkArgs& a, hipStream_t s, int num_cus);
 hipError_t launch_walk_place(const WalkArgs& a, hipStream_t s, int num_cus);
 
+// bsg_engine_gc_mark / bsg_engine_gc_compact (bsgpu_gc.inc). w is the walk's block for the pool,
+// its index, the level at hand and the count pass (w.hdr = &g->w, w.ns = 1 with w.sizes and
+// w.status at g's spare words; every frontier entry is kWalkNoCover). Everything but the pool and
+// the compaction's output belongs to the mark.
+struct GcArgs {
+  WalkArgs w;
+  GcHdr* g;
+  const uint8_t* roots;      // [nroots * 32]
+  uint64_t nroots;
+  uint64_t* rblob;           // [nroots] a Root's blob, or kWalkDead
+  uint32_t* rstatus;         // [nroots] kWalkCorrupt / kWalkNotFound
+  uint32_t forgive;          // BSG_GC_MISSING_LEAVES
+  uint8_t* live;             // [nblobs] zeroed per mark
+  uint32_t* state;           // [nblobs] kGcClaimed | kGcFailed, zeroed per mark
+  uint64_t* rank;            // [nblobs + 1] exclusive prefix of live
+  uint64_t* noff;            // [nblobs + 1] ... of the live blobs' lens: the new offsets
+  uint64_t* noff16;          // [nblobs + 1] ... each len rounded up to 16
+  uint64_t* part;            // [sum_parts(nblobs)] workgroup sums of a prefix pass
+  uint64_t* mtab;            // k_gc_missing: pool offsets of missing `leaves` refs, by ref
+  uint64_t mmask;
+  const uint64_t* coff;      // k_gc_compact: noff or noff16
+  uint64_t total;            //   the output's bytes
+  uint8_t* out;
+};
+hipError_t launch_gc_roots(const GcArgs& a, hipStream_t s, int num_cus);
+// after launch_walk_count(a.w): the failed nodes' verdicts, then one thread per child
+hipError_t launch_gc_emit(const GcArgs& a, hipStream_t s, int num_cus);
+hipError_t launch_gc_status(const GcArgs& a, hipStream_t s, int num_cus);
+// the level's `leaves` children once more: the distinct refs the pool lacks (a.w.nchild children)
+hipError_t launch_gc_missing(const GcArgs& a, hipStream_t s, int num_cus);
+hipError_t launch_gc_offsets(const GcArgs& a, hipStream_t s, int num_cus);
+hipError_t launch_gc_compact(const GcArgs& a, hipStream_t s);
+
 }  // namespace bsg

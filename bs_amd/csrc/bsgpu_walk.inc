@@ -174,8 +174,10 @@ __global__ __launch_bounds__(256) void k_wk_count(WalkArgs a) {
       } else {
         bad = true;
       }
-      bad = bad || pos != len || count == 0 || first != noff || noff + size < noff ||
-            noff != it.exp_off || (it.exp_size && size != it.exp_size);
+      bad = bad || pos != len || count == 0 || first != noff || noff + size < noff;
+      // (a kWalkNoCover entry is held to the node's own rules alone: bsg_engine_gc_mark)
+      if (!(it.flags & kWalkNoCover))
+        bad = bad || noff != it.exp_off || (it.exp_size && size != it.exp_size);
     }
     if (lane == 0) {
       const bool live = b && !bad;

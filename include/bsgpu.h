@@ -417,6 +417,83 @@ int bsg_engine_restore_walk(bsg_engine* eng,
                             uint8_t* d_out, uint64_t out_cap, const uint64_t* out_off,
                             uint32_t nstreams, int flags, bsg_restore_info* info);
 
+/* ---- a pool garbage-collected on the device from its Roots: gc.Protect + split.Protect + gc.Run ---- */
+/* The mark (gc.Protect with split.Protect, gc/gc.go:38-97 and split/split.go:306-322) finds the
+ * blobs of a pool that a set of Roots reaches; the sweep (gc.Run's Deletes, as a compaction)
+ * gathers them into a new pool.
+ * Pool and Roots. The pool means what it means for bsg_engine_walk: blobs may start at any byte,
+ * refs are trusted labels and nothing is hashed; of two blobs under one ref only the one with the
+ * smaller index is ever used, the other is dead. roots is any number of refs up to 2^32 - 1 (it is
+ * not bounded by 65,535). 32 zero bytes is bs.Zero and is skipped with status BSG_OK. The same
+ * Root may appear many times. Any node blob may be a Root, and its offset is not held to 0
+ * (gc.Protect starts anywhere).
+ * What is live. A blob is live if it is the smallest-index blob of a ref that is a Root, or that an
+ * expanded node names under `nodes` or `leaves`. A blob is expanded, once, if it is live through a
+ * Root or a `nodes` entry; a blob named only by `leaves` entries is never read; a blob named both
+ * ways is expanded.
+ * Node rules. An expanded blob must meet the walk's per-node rules: exactly PutProto's bytes;
+ * children of one kind, and at least one; the first child's offset equals the node's offset; child
+ * offsets strictly ascend; size > 0, and offset + size does not wrap. The walk's edge rules do
+ * not apply: a child is not held to its cover and a leaf's len is not compared, because
+ * split.Protect follows refs and nothing else; bsg_engine_walk and bsg_engine_restore check the
+ * covers when the data is read. A node that fails is not expanded further. A `nodes` entry of a
+ * node at depth 64 is refused unread; a node's depth is the fewest edges from any Root, so a chain
+ * of 100 nodes with a Root every 50 passes. A cycle of trusted labels ends because a blob is
+ * expanded once.
+ * Verdicts. status[r] speaks of Root r alone: BSG_ENOTFOUND if it is not in the pool,
+ * BSG_ECORRUPT if its own blob fails the node rules, else BSG_OK. Everything below the Roots is
+ * reported through bad_blob. Returns, in this order: BSG_EINVAL, before anything is enqueued, for
+ * a null pointer with a non-zero count, a blob that ends past pool_bytes, or unknown flag bits;
+ * BSG_ENOTFOUND if a Root, a `nodes` ref or (without BSG_GC_MISSING_LEAVES) a `leaves` ref of an
+ * expanded node that passed its rules is not in the pool; BSG_ECORRUPT if an expanded node breaks
+ * a rule or sits too deep; BSG_ESTATE if the engine has an enqueued, unfinished run; BSG_ENOMEM.
+ * A failed mark publishes nothing and drops the previous mark's result, so a caller can never
+ * sweep on a half-read tree. The set of expanded blobs, and every output, is a function of the
+ * arguments alone: two calls give identical bytes. Synchronous, on the engine's stream. The
+ * engine's last run, dedup result, tree, walk and restore buffers are not touched, and an engine
+ * needs no run before it marks.
+ * On success the engine keeps, until its next mark: live[k], one byte per pool blob, 0 or 1; and
+ * the live blobs' new offsets, the exclusive prefix sum of len over the live blobs in index order,
+ * once as it is and once with every term rounded up to 16 (BSG_GC_ALIGN16 in the flags of
+ * bsg_engine_copy_gc and bsg_engine_gc_compact chooses). What gc.Run would Delete is
+ * {blobs[k].ref : live[k] == 0}, minus the refs that a live smaller-index twin still carries. */
+#define BSG_GC_MISSING_LEAVES 1  /* mark: a `leaves` ref the pool lacks is no error */
+#define BSG_GC_ALIGN16        1  /* compact: every blob starts at a multiple of 16 */
+typedef struct bsg_gc_info {
+  uint64_t bad_root;        /* smallest root index whose status is not BSG_OK, else UINT64_MAX */
+  uint64_t bad_blob;        /* smallest pool index of a visited node that fails its rules, or (if none does)
+                               that names a child the pool lacks; else UINT64_MAX */
+  uint64_t nlive, live_bytes;   /* 0 on any failure */
+  uint64_t ndead, dead_bytes;   /* 0 on any failure */
+  uint64_t nnodes;          /* distinct node blobs expanded (filled whenever the layout was valid) */
+  uint64_t missing_leaves;  /* distinct `leaves` refs not in the pool (only with the flag, else 0) */
+  uint32_t depth;           /* largest depth of an expanded node; a node's depth = fewest edges from any Root */
+  uint32_t reserved;
+} bsg_gc_info;
+int bsg_engine_gc_mark(bsg_engine* eng, const uint8_t* d_pool, uint64_t pool_bytes,
+                       const bsg_pool_blob* blobs, uint64_t nblobs,   /* host */
+                       const uint8_t* roots, uint64_t nroots,         /* host, nroots x 32 */
+                       int flags, int32_t* status /* host, nroots, or NULL */, bsg_gc_info* info);
+/* The last successful mark to host memory: live, up to cap_live entries, and
+ * table[j] = {new_off, len, ref} of the j-th live blob in index order, up to cap_table entries:
+ * the `blobs` argument of bsg_engine_walk and bsg_engine_restore on the compacted pool. Either
+ * pointer may be NULL. BSG_ESTATE without a successful mark (as the device pointer below is
+ * NULL); BSG_EINVAL for unknown flag bits. */
+int bsg_engine_copy_gc(bsg_engine* eng, uint8_t* live, uint64_t cap_live,
+                       bsg_pool_blob* table, uint64_t cap_table, int flags);
+const uint8_t*  bsg_engine_gc_live_device(const bsg_engine* eng);
+/* The sweep: for every live blob, d_out[new_off[j] .. + len) = that blob's bytes, in index order.
+ * With BSG_GC_ALIGN16 the padding bytes between blobs are written zero, so the output meets
+ * BSG_RESTORE_VERIFY's alignment rule. *out_bytes is the end of the last live blob's bytes (0 if
+ * nothing is live); no byte of d_out outside [d_out, d_out + *out_bytes) is written. Blobs of
+ * len 0 occupy nothing. Before anything is enqueued: BSG_ESTATE without a mark (or with an
+ * unfinished run); BSG_EINVAL if d_pool / pool_bytes are not the mark's, if d_out is null or not
+ * a multiple of 16, if cap is less than the packed size, for unknown flag bits, or if the output
+ * range intersects the pool: in-place compaction is out of scope. The caller keeps the pool
+ * valid and unchanged from the mark until the call returns. Synchronous. */
+int bsg_engine_gc_compact(bsg_engine* eng, const uint8_t* d_pool, uint64_t pool_bytes,
+                          uint8_t* d_out, uint64_t cap, int flags, uint64_t* out_bytes);
+
 /* Per-stage HIP event timing of later runs, and the last finished run's stage durations in
  * ms: [0] rolling scan (k_scan), [1] prefix/compact/select/chunks, [2] SHA-256 (k_sha, and the
  * early chains' tail). Timed on the engine's own stream. enable: 0 off, 1 every stage (four
