@@ -23,9 +23,10 @@ _RANK = {0: OK, 1: ECORRUPT, 2: ENOTFOUND}
 # ---- the model ---------------------------------------------------------------------------------
 def index_of(blobs) -> dict:
     """ref -> the smallest blob index that carries it."""
+    raw = np.ascontiguousarray(blobs["ref"]).tobytes()
     index = {}
-    for k, b in enumerate(blobs):
-        index.setdefault(b["ref"].tobytes(), k)
+    for k in range(len(blobs)):
+        index.setdefault(raw[32 * k:32 * k + 32], k)
     return index
 
 
@@ -65,7 +66,7 @@ def mark(blob_bytes, blobs, roots, pool_bytes, flags=0):
     info = {"bad_root": NONE, "bad_blob": NONE, "nlive": 0, "live_bytes": 0, "ndead": 0,
             "dead_bytes": 0, "nnodes": 0, "missing_leaves": 0, "depth": 0}
     if flags & ~GC_MISSING_LEAVES or nr >= 1 << 32 or \
-            any(int(b["off"]) + int(b["len"]) > pool_bytes for b in blobs):
+            any(o + n > pool_bytes for o, n in zip(blobs["off"].tolist(), blobs["len"].tolist())):
         return EINVAL, None, info, None
     index = index_of(blobs)
     live, claimed, failed, missing = set(), set(), set(), set()
@@ -288,6 +289,42 @@ def len_mix(pattern: str, seed: int = 11):
         roots = [W.sha(ln)]
     pool, blobs = pool_from(ent, first=3)
     return pool, blobs, roots
+
+
+def edge_pool(drop=()):
+    """walk_cases.edge_nodes as five Roots of one tiny pool, offsets up to 2^64 - 2 and every
+    entry length in it: (pool, blobs, roots). The leaves they name lie between the nodes, a blob
+    nobody names among them; the leaves whose refs are in `drop` are left out."""
+    nodes = W.edge_nodes()
+    dead = b"named by nobody"
+    ent = [(r, b) for r, b in W.wide_leaves().items() if r not in drop] + [(W.sha(dead), dead)]
+    for i, n in enumerate(nodes):
+        ent.insert(2 * i, (n["ref"], n["bytes"]))
+    pool, blobs = pool_from(ent)
+    return pool, blobs, [n["ref"] for n in nodes]
+
+
+def many_roots(nroots: int, malformed: bool = False):
+    """nroots Roots over three three_level trees: all but the last two repeat the first tree's
+    Root or are zero (every fifth), the last two name the second and the third tree, which are
+    live through them alone. malformed: the third tree's Root blob is padded by a byte.
+    (pool, blobs, roots, [the blob indices of tree j])."""
+    assert nroots >= 3
+    trees, store = [], {}
+    for j in range(3):
+        t, lstore = W.three_level(30 + j)
+        trees.append(t)
+        store.update(lstore)
+        store.update(t.store())
+    if malformed:
+        n = trees[2].nodes[0][0]
+        store[n["ref"]] = W.FAMILIES["padded"][0](n)
+    pool, blobs = W.pool_of(store)
+    index = index_of(blobs)
+    own = [sorted({index[n["ref"]] for lv in t.nodes for n in lv}
+                  | {index[r] for n in t.nodes[2] for r, _ in n["kids"]}) for t in trees]
+    roots = [bytes(32) if r % 5 == 4 else trees[0].root for r in range(nroots - 2)]
+    return pool, blobs, roots + [trees[1].root, trees[2].root], own
 
 
 # ---- the device against the model (tests/test_gpu_gc*.py) --------------------------------------

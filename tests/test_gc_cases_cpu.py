@@ -141,3 +141,73 @@ def test_case_builders_mean_what_they_say():
     pool, blobs, roots = W.chain(99)
     rc, _, info, live = G.run_model(pool, blobs, roots + [blobs[50]["ref"].tobytes()])
     assert rc == G.OK and info["depth"] == 49 and live.all()
+
+
+# ---- the builders of test_gpu_gc_wide.py -----------------------------------------------------------
+def test_edge_pool():
+    pool, blobs, roots = G.edge_pool()
+    rc, status, info, live = G.run_model(pool, blobs, roots)
+    assert rc == G.OK and status.tolist() == [0] * 5 and info["nnodes"] == 5
+    assert info["ndead"] == 1 and info["depth"] == 0
+    index = G.index_of(blobs)
+    for e in (45, 46, 47):
+        assert live[index[W.sha(W.only_leaf(e))]] == 1
+    view = {blobs[k]["ref"].tobytes(): W.getter(pool, blobs)(k) for k in range(len(blobs))}
+    assert {index[r] for r in G.protect(view, roots)} == set(np.flatnonzero(live).tolist())
+    # the walk holds every child to its cover: it refuses these nodes, which is why the mark
+    # carries them
+    assert W.run_model(pool, blobs, roots[:1])[0] == W.ECORRUPT
+    # each only_leaf is live through its own entries: without the three all_lengths nodes and the
+    # node at 2^63, none is
+    assert G.run_model(pool, blobs, roots[3:4])[2]["nlive"] == 2
+    gone = W.sha(W.only_leaf(47))
+    pool, blobs, roots = G.edge_pool(drop=[gone])
+    assert G.run_model(pool, blobs, roots)[0] == G.ENOTFOUND
+    rc, status, info, live = G.run_model(pool, blobs, roots, flags=G.GC_MISSING_LEAVES)
+    assert rc == G.OK and info["missing_leaves"] == 1
+    assert sum(r == gone for n in W.edge_nodes() for r, _ in n["kids"]) == 4
+
+
+@pytest.mark.parametrize("name,lane", W.WIDE_CASES)
+def test_wide_faults_give_the_walks_verdict(name, lane):
+    pool, blobs, roots, k = W.wide_mutated(name, lane)
+    wrc = W.run_model(pool, blobs, roots)[0]
+    rc, status, info, live = G.run_model(pool, blobs, roots)
+    assert rc == wrc == G.ECORRUPT and live is None
+    assert info["bad_blob"] == k and info["bad_root"] == 1 and status.tolist() == [0, G.ECORRUPT]
+    # the node as it was passes the mark
+    n = W.wide_target(name, lane)[0] if name != "wrap_2_63" else W.edge_nodes()[4]
+    assert n["ref"] == roots[1]
+    pool, blobs = G.pool_from(list(W.wide_leaves().items()) + [(n["ref"], n["bytes"])])
+    assert G.run_model(pool, blobs, roots[1:])[0] == G.OK
+
+
+def test_grid_pass_builders_mean_what_they_say():
+    t, n = W.grid_threads(1), W.count_waves(1)
+    pool, blobs, roots = G.wide(n + 3)
+    rc, _, info, live = G.run_model(pool, blobs, roots)
+    assert rc == G.OK and info["nnodes"] == n + 4 and live.all()
+    # the walk accepts wide() as well: a level of t + 3 nodes under a `nodes` node of t + 3 entries
+    pool, blobs, roots = G.wide(t + 3)
+    rc, _, info, recs, sizes, counts = W.run_model(pool, blobs, roots)
+    assert rc == W.OK and info["nnodes"] == t + 4 and info["depth"] == 1
+    assert counts.tolist() == [t + 3] and sizes.tolist() == [10 * (t + 3)]
+    assert len(W.parse_node(W.getter(pool, blobs)(len(blobs) - 1))[1]) == t + 3
+    pool, blobs, roots, own = G.many_roots(t + 5)
+    assert len(roots) == t + 5 and set(roots[:-2]) == {roots[0], bytes(32)}
+    assert len({roots[0], roots[-2], roots[-1]}) == 3 and not set(own[1]) & set(own[2])
+    rc, status, info, live = G.run_model(pool, blobs, roots)
+    assert rc == G.OK and live.all() and info["nnodes"] == 39
+    live = G.run_model(pool, blobs, roots[:-2])[3]
+    assert not live[own[1]].any() and not live[own[2]].any() and live[own[0]].all()
+    pool, blobs, roots, own = G.many_roots(t + 5, malformed=True)
+    rc, status, info, live = G.run_model(pool, blobs, roots)
+    assert rc == G.ECORRUPT and status[-1] == G.ECORRUPT and not status[:-1].any()
+    assert info["bad_root"] == t + 4 and info["bad_blob"] == G.index_of(blobs)[roots[-1]]
+    nblobs = 2 * (t + 7)
+    pool, blobs, roots, flags = G.sized_pool(nblobs)
+    rc, _, info, live = G.run_model(pool, blobs, roots, flags=flags)
+    k = G.index_of(blobs)[roots[0]]
+    assert rc == G.OK and len(blobs) == nblobs > 2 * t and info["nlive"] == t + 8
+    assert len(W.parse_node(W.getter(pool, blobs)(k))[1]) == t + 7 and info["nnodes"] == 1
+    assert -(-nblobs // W.grid_caps()["kSumTile"]) > 2

@@ -146,13 +146,13 @@ def test_many_streams_and_a_wide_node(gpu, eng):
 
 
 # ---- 3. stride changes inside one node ---------------------------------------------------------
-def _stride_case(gpu, eng, thresholds, bmax, tail):
+def _stride_case(gpu, eng, thresholds, bmax, tail, gmax=1 << 14):
     """One walk of three streams, the entry length changing first (lane 0), in the middle (32)
     and last (63) of a 64-entry group. The leaves all alias one unwritten stretch of bmax bytes
     after the node blobs: the walk reads no leaf byte."""
     nodes, roots, ent, lanes = [], [], {}, []
     for lane in (0, 32, 63):
-        lens = W.crossing_lens(thresholds, bmax, lane, tail)
+        lens = W.crossing_lens(thresholds, bmax, lane, tail, gmax)
         ch = W.stride_lanes(lens)
         assert len(ch) == 1 + len(thresholds) and all(ln == lane for _, ln in ch[1:])
         b, root, leaves = W.stride_node(lens, 0)
@@ -187,7 +187,7 @@ def test_stride_changes_small_offsets(gpu, eng):
 
 def test_stride_changes_large_offsets(gpu, eng):
     """Offsets cross 2^35 and 2^42 as well: a 1 GiB blob, left unwritten, repeated 4,100 times.
-    (Varints of 8 to 10 bytes need streams of 2^49 bytes and more)"""
+    (2^49 is crossed in test_gpu_walk_wide.py; varints of 9 and 10 bytes: DESIGN §4.10.)"""
     want = _stride_case(gpu, eng, [1 << 7, 1 << 14, 1 << 21, 1 << 28, 1 << 35, 1 << 42],
                         1 << 30, 40)
     assert (want[3]["len"] == 1 << 30).sum() >= 3 * 4100 and int(want[4].max()) > 1 << 42

@@ -7,6 +7,8 @@ per-stream status ranking. tests/test_walk_cases_cpu.py holds it to the oracle's
 from __future__ import annotations
 
 import hashlib
+import os
+import re
 
 import numpy as np
 
@@ -91,11 +93,12 @@ def model(blob_bytes, blobs, roots, pool_bytes, flags=0):
     rc is OK."""
     ns = len(roots)
     info = {"bad_stream": NONE, "nrecs": 0, "nnodes": 0, "bytes": 0, "depth": 0}
-    if flags != 0 or ns > 65535 or any(int(b["off"]) + int(b["len"]) > pool_bytes for b in blobs):
+    if flags != 0 or ns > 65535 or any(
+            o + n > pool_bytes for o, n in zip(blobs["off"].tolist(), blobs["len"].tolist())):
         return EINVAL, None, info, None, None, None
-    index = {}
-    for k, b in enumerate(blobs):
-        index.setdefault(b["ref"].tobytes(), k)
+    raw, index = np.ascontiguousarray(blobs["ref"]).tobytes(), {}
+    for k in range(len(blobs)):
+        index.setdefault(raw[32 * k:32 * k + 32], k)
     rank, sizes, recs = [0] * ns, [0] * ns, []
 
     def fail(s, r):
@@ -159,8 +162,12 @@ def model(blob_bytes, blobs, roots, pool_bytes, flags=0):
 def table_of(entries) -> np.ndarray:
     """A bsg_pool_blob table from (off, len, ref) triples."""
     t = np.zeros(len(entries), dtype=POOL_BLOB_DTYPE)
-    for k, (off, ln, ref) in enumerate(entries):
-        t[k] = (off, ln, np.frombuffer(ref, dtype=np.uint8))
+    if len(entries):
+        assert all(len(ref) == 32 for _, _, ref in entries)
+        t["off"] = np.array([off for off, _, _ in entries], dtype=np.uint64)
+        t["len"] = np.array([ln for _, ln, _ in entries], dtype=np.uint64)
+        t["ref"] = np.frombuffer(b"".join(bytes(ref) for _, _, ref in entries),
+                                 dtype=np.uint8).reshape(-1, 32)
     return t
 
 
@@ -418,15 +425,16 @@ def stride_lanes(lens):
     return out
 
 
-def crossing_lens(thresholds, bmax: int, lane: int, tail: int):
+def crossing_lens(thresholds, bmax: int, lane: int, tail: int, gmax: int = 1 << 14):
     """Leaf lengths (each at most bmax) of one leaf node whose children's offsets reach every
     threshold exactly, so that the entry length changes there, each change `lane` entries (modulo
     64) after the one before; then `tail` more leaves of bmax bytes. A stretch is as many bmax
-    leaves as fit, one leaf for the rest and 1-byte leaves to make up the count."""
+    leaves as fit, one leaf for the rest and 1-byte leaves to make up the count, fewer than gmax
+    entries in all."""
     lens, at = [1], 1  # child 0 at offset 0 (36 bytes), child 1 at offset 1: the first change
     for t in thresholds:
         d = t - at
-        for g in range(1, 1 << 14):
+        for g in range(1, gmax):
             k = min((d - 1) // bmax, g - 1)
             rest = d - k * bmax - (g - k - 1)  # what the one odd leaf must hold
             if g % 64 == lane and (g == k and rest == 0 or g > k and 1 <= rest <= bmax):
@@ -449,6 +457,231 @@ def stride_node(lens, pool_off: int, first: int = 0):
         o += n
     b = O.proto_node([], kids, first, o - first)
     return b, sha(b), [(pool_off, n, r) for n, r in sorted(labels.items())]
+
+
+# ---- entries of 45 to 47 bytes: offsets up to 2^64 - 1 -------------------------------------------
+# An accepted walk cannot reach them all (a leaf is at most the pool, so offsets of 2^56 and more
+# need 2^26 leaves of 1 GiB); a mark holds no child to a cover, so there a tiny pool can.
+THRESHOLDS = [1 << (7 * j) for j in range(10)]  # the offsets at which an entry grows by a byte
+ENTRY_LENS = [36] + list(range(38, 48))
+COMMON_LEAF = b"the common leaf"
+
+
+def entry_len(off: int) -> int:
+    return 36 if off == 0 else 37 + varint_len(off)
+
+
+def offset_lanes(offsets):
+    """stride_lanes for a node given by its children's offsets."""
+    out, start, prev = [], 0, None
+    for i, o in enumerate(offsets):
+        e = entry_len(o)
+        if prev is not None and e != prev:
+            out.append((i, (i - start) % 64))
+            start = i
+        prev = e
+    return out
+
+
+def all_lengths_offsets(lane: int, tail: int = 2):
+    """Ascending child offsets of a node with all eleven entry lengths (36, 38 .. 47): child 0 at
+    0, then for every threshold t = 2^(7j) a run from t on that ends at the next threshold - 1
+    (the last one at 2^64 - 2), so both sides of every varint edge are present. Every run but the
+    last holds `lane` entries modulo 64 (at least two), so every change of the entry length after
+    the first (child 1, lane 1) lies on `lane` of its 64-entry group; the last run holds `tail`."""
+    assert 0 <= lane < 64 and tail >= 2
+    g = lane if lane >= 2 else lane + 64
+    offs = [0]
+    for j, t in enumerate(THRESHOLDS):
+        n = g if j < 9 else tail
+        end = THRESHOLDS[j + 1] - 1 if j < 9 else (1 << 64) - 2
+        offs += [t + i for i in range(n - 1)] + [end]
+    return offs
+
+
+def only_leaf(elen: int) -> bytes:
+    """The leaf blob that offsets_node's entries of elen bytes (45, 46 or 47) alone name."""
+    return b"named by entries of %d bytes alone" % elen
+
+
+def offsets_node(offsets, size: int = 1):
+    """A leaf node over children at `offsets` (its own offset: the first child's), in Tree._node's
+    form. Every child names COMMON_LEAF, but the last entry of each run of 45, 46 and 47 bytes
+    names only_leaf(its length), so that leaf is live only if that very entry was read."""
+    kids = []
+    for i, o in enumerate(offsets):
+        e = entry_len(o)
+        last = i + 1 == len(offsets) or entry_len(offsets[i + 1]) != e
+        kids.append((sha(only_leaf(e)) if e >= 45 and last else sha(COMMON_LEAF), o))
+    return Tree._node(2, kids, offsets[0], size)
+
+
+def wide_leaves() -> dict:
+    """{ref: bytes} of the leaves offsets_node names."""
+    return {sha(b): b for b in [COMMON_LEAF] + [only_leaf(e) for e in (45, 46, 47)]}
+
+
+def edge_nodes():
+    """The accepted nodes of the offsets' upper edge: all_lengths_offsets on lanes 0, 32 and 63
+    with size 1 (`20 01`); one child at offset 0 with size 2^64 - 1 (a 10-byte varint whose last
+    byte is 1); and a node at its own offset 2^63 (an `18` field of 10 bytes) with size 2^63 - 1,
+    so that offset + size is 2^64 - 1."""
+    out = [offsets_node(all_lengths_offsets(lane)) for lane in (0, 32, 63)]
+    out.append(offsets_node([0], size=(1 << 64) - 1))
+    out.append(offsets_node([(1 << 63) + i for i in range(3)], size=(1 << 63) - 1))
+    return out
+
+
+def _entries(n):
+    return [b"\x12" + O._varint(len(c)) + c for c in (O.proto_child(r, o) for r, o in n["kids"])]
+
+
+def _respliced(n, k: int, new: bytes, insert: bool = False) -> bytes:
+    e = _entries(n)
+    assert len(e[k]) == 47
+    e[k:k + (0 if insert else 1)] = [new]
+    tail = (b"\x18" + O._varint(n["offset"]) if n["offset"] else b"") + b"\x20" + \
+        O._varint(n["size"])
+    return b"".join(e) + tail
+
+
+def _e47(n, k: int) -> bytes:
+    return _entries(n)[k]
+
+
+# name -> ((node, k) -> new bytes): entry k, one of 47 bytes, made a fault of the 10-byte varint's
+# rules. Every one is ECORRUPT by the node's form alone. Only the mark's verdict shows it: the
+# walk refuses these nodes for their covers anyway.
+WIDE_FAMILIES = {
+    # the tenth byte 2: an offset of 2^64 and more
+    "ends_02": lambda n, k: _respliced(n, k, _e47(n, k)[:-1] + b"\x02"),
+    # the tenth byte goes on, and an eleventh follows the entry's 47 bytes
+    "continues": lambda n, k: _respliced(n, k, _e47(n, k)[:-1]
+                                         + bytes([_e47(n, k)[-1] | 0x80, 0x01])),
+    # the tenth byte 0: not minimal
+    "ends_00": lambda n, k: _respliced(n, k, _e47(n, k)[:-1] + b"\x00"),
+    # length byte 46, an entry of 48 bytes with a varint of eleven
+    "len_byte_46": lambda n, k: _respliced(n, k, b"\x12\x2e" + _e47(n, k)[2:-1]
+                                           + bytes([_e47(n, k)[-1] | 0x80, 0x01])),
+    # an entry of 46 bytes after those of 47: the lengths fall, and so do the offsets
+    "len_47_then_46": lambda n, k: _respliced(
+        n, k, b"\x12" + O._varint(44) + O.proto_child(sha(COMMON_LEAF), (1 << 56) + k), True),
+}
+WIDE_LANES = (0, 5)
+
+
+def _alone(last: int):
+    """An entry of 47 bytes put in before entry k, its varint nine bytes of ff and then `last`:
+    the low 64 bits of what it spells are 2^63 - 1 whether `last` is 2 or 0."""
+    return lambda n, k: _respliced(n, k, b"\x12" + O._varint(45) + O.proto_child(
+        sha(COMMON_LEAF), 1)[:-1] + b"\xff" * 9 + bytes([last]), True)
+
+
+# ends_02 and ends_00 above sit in a run that starts at 2^63 after a child at 2^63 - 1, so a
+# parser that kept the low 64 bits alone (0, or 5 on lane 5) would still refuse them, by the
+# ascending rule. These two can be refused by the tenth byte's own rule alone: the child before
+# is at 2^63 - 2, the low 64 bits of the entry are 2^63 - 1 and the next child is at 2^63, so the
+# offsets ascend and the rest of the node is valid. Lane 0 only: a later lane's elder in a run of
+# 47-byte entries is at 2^63 at least.
+WIDE_ALONE = {"ends_02_alone": _alone(0x02), "ends_00_alone": _alone(0x00)}
+WIDE_FAMILIES.update(WIDE_ALONE)
+
+
+def wide_target(name: str, lane: int):
+    """(node, k): all_lengths_offsets(0, 70)'s node and the entry the family `name` changes so
+    that the fault lies on `lane` of a 64-entry group of 47-byte entries: the run's first entry
+    (for the entry put in after the 47-byte ones: after 64 of them) or `lane` later. For the
+    WIDE_ALONE families the node's child at 2^63 - 1 lies at 2^63 - 2 instead, and k is the first
+    47-byte entry, which the new one goes before."""
+    offs = all_lengths_offsets(0, 70)
+    if name in WIDE_ALONE:
+        assert lane == 0
+        offs[offs.index((1 << 63) - 1)] -= 1
+    n = offsets_node(offs)
+    first = offset_lanes([o for _, o in n["kids"]])[-1][0]
+    return n, first + lane + (64 if name == "len_47_then_46" and lane == 0 else 0)
+
+
+def wide_mutated(name: str, lane: int, seed: int = 1):
+    """(pool, blobs, roots, the changed blob's index): a three_level tree as Root 0 and, as Root
+    1, wide_target's node with the family applied (or, for "wrap_2_63", the node at offset 2^63
+    with size 2^63), under its unchanged label."""
+    t, lstore = three_level(seed)
+    store = {**lstore, **t.store(), **wide_leaves()}
+    if name == "wrap_2_63":
+        n = offsets_node([(1 << 63) + i for i in range(3)], size=(1 << 63) - 1)
+        bad = encode(n, tags=[0x12] * 3, size=1 << 63)
+    else:
+        n, k = wide_target(name, lane)
+        bad = WIDE_FAMILIES[name](n, k)
+    assert n["ref"] not in store and bad != n["bytes"]
+    store[n["ref"]] = bad
+    pool, blobs = pool_of(store)
+    return pool, blobs, [t.root, n["ref"]], len(store) - 1
+
+
+WIDE_CASES = [(name, lane) for name in sorted(WIDE_FAMILIES) for lane in WIDE_LANES
+              if lane == 0 or name not in WIDE_ALONE] + [("wrap_2_63", 0)]
+
+
+# ---- more than one grid pass -------------------------------------------------------------------
+CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "bs_amd", "csrc")
+
+
+def grid_caps() -> dict:
+    """What caps a launch of the walk's, the mark's and the restore's grid-stride kernels, read
+    from the source: engine_grid's workgroups per CU (of 256 threads), launch_walk_count's (of 4
+    waves, a node each) and the prefix sum's tile."""
+    out = {}
+
+    def one(fn, pattern, name):
+        with open(os.path.join(CSRC, fn)) as f:
+            m = re.findall(pattern, f.read(), re.M)
+        assert len(m) == 1, (name, m)
+        out[name] = int(m[0])
+
+    one("bsgpu_engine_common.inc",
+        r"^\s*return grid_for\(items, 256, (\d+)u \* \(uint32_t\)num_cus\);", "grid_wgs_per_cu")
+    one("bsgpu_walk.inc", r"cap = (\d+)ull \* \(uint32_t\)num_cus;", "count_wgs_per_cu")
+    one("bsgpu_engine_common.inc", r"^constexpr\s+uint32_t\s+kSumTile\s*=\s*(\d+)\s*;", "kSumTile")
+    return out
+
+
+def grid_threads(cus: int) -> int:
+    """T: the threads of one pass of an engine_grid launch; item T is a thread's second trip."""
+    return grid_caps()["grid_wgs_per_cu"] * cus * 256
+
+
+def count_waves(cus: int) -> int:
+    """N: the waves of one pass of k_wk_count; node N is a wave's second trip."""
+    return grid_caps()["count_wgs_per_cu"] * cus * 4
+
+
+def many_streams(n3: int):
+    """n3 streams that cycle three distinct three_level trees, with an empty stream (a zero Root)
+    put in at place 7, a mixed_depth tree at place 11, and mixed_depth, empty, mixed_depth as the
+    last three: (pool, blobs, roots, kinds, data), kinds[s] in 0, 1, 2, "m", "z" naming stream
+    s's tree and data[kind] its bytes."""
+    assert n3 >= 12
+    trees, store, data = [], {}, {"z": b""}
+    for j in range(3):
+        t, lstore = three_level(20 + j)
+        trees.append(t)
+        store.update(lstore)
+        store.update(t.store())
+        data[j] = b"".join(lstore[r] for lv in t.nodes[2:] for n in lv for r, _ in n["kids"])
+    mpool, mblobs, mroots, mleaves = mixed_depth()
+    get = getter(mpool, mblobs)
+    store.update({mblobs[k]["ref"].tobytes(): get(k) for k in range(len(mblobs))})
+    data["m"] = b"".join(mleaves)
+    kinds = [s % 3 for s in range(n3)]
+    kinds.insert(7, "z")
+    kinds.insert(11, "m")
+    kinds += ["m", "z", "m"]
+    assert len(kinds) <= 65535
+    root = {0: trees[0].root, 1: trees[1].root, 2: trees[2].root, "m": mroots[0], "z": bytes(32)}
+    pool, blobs = pool_of(store)
+    return pool, blobs, [root[k] for k in kinds], kinds, data
 
 
 # ---- the device against the model (tests/test_gpu_walk*.py) ------------------------------------
