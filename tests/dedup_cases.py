@@ -3,7 +3,8 @@
 The model is a dict from ref bytes to first index over the ORACLE's records of the same bytes;
 expected first / uniq / pack_off and the packed bytes follow from it. Every builder returns host
 streams (uint8 arrays) and the split parameters; tests/test_dedup_cpu.py holds each builder to
-the properties it claims, tests/test_gpu_dedup.py runs them on the device."""
+the properties it claims, tests/test_gpu_dedup.py and tests/test_gpu_dedup_wide.py run them on
+the device."""
 from __future__ import annotations
 
 import os
@@ -195,3 +196,190 @@ def planted_refs() -> np.ndarray:
 
 def random_refs(seed: int, n: int) -> np.ndarray:
     return np.random.default_rng(seed).integers(0, 256, (n, 32), dtype=np.uint8)
+
+
+# ---- more than one grid pass, and the table's end (tests/test_gpu_dedup_wide.py) --------------
+def wide_counts(cus: int):
+    """(T, N0). T: the threads of one pass of an engine_grid launch on `cus` CUs, so item T is a
+    thread's second trip; N0 = max(T, 256 x kSumTile): from N0 items on k_sum_mid also sums two
+    parts per thread. Both from the source (walk_cases.grid_caps)."""
+    import walk_cases as W
+    t = W.grid_threads(cus)
+    return t, max(t, 256 * W.grid_caps()["kSumTile"])
+
+
+def packed_gather(streams, recs, uniq) -> bytes:
+    """packed() as one numpy gather, for runs of several hundred thousand records."""
+    host, off, _ = place(streams)
+    u = np.asarray(uniq, dtype=np.int64)
+    lens = recs["len"][u].astype(np.int64)
+    src = np.asarray(off, dtype=np.int64)[recs["stream"][u]] + recs["offset"][u].astype(np.int64)
+    dst = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    return host[np.repeat(src - dst[:-1], lens) + np.arange(dst[-1])].tobytes()
+
+
+def wide_facts(recs, first, uniq, t: int, main: int) -> dict:
+    """What wide_run claims, counted from the records and the model's result: the records, the new
+    ones, those whose first occurrence lies more than t records back, the duplicates inside
+    stream `main` and the distinct record lengths."""
+    f = np.asarray(first, dtype=np.int64)
+    i = np.arange(len(f))
+    return {"nrec": len(recs), "nunique": len(uniq), "far": int((f < i - t).sum()),
+            "dups_in_main": int(((f < i) & (recs["stream"] == main)).sum()),
+            "nlens": len(np.unique(recs["len"]))}
+
+
+def wide_ok(facts: dict, t: int, n0: int) -> bool:
+    return (facts["nrec"] > n0 + 100 and facts["nunique"] > t + 100 and facts["far"] >= 1000
+            and facts["dups_in_main"] >= 1000 and facts["nlens"] >= 16)
+
+
+WIDE_EXCERPTS = 80
+
+
+def wide_run(O, table, cus: int):
+    """A run of more than N0 new records: ((streams, bits, min_size), the oracle's records).
+    Streams: 80 excerpts of 2,000 bytes spread over the main stream (their chunks are duplicates
+    where the main stream reaches them, so rank[i] departs from i early); the main stream,
+    SplitMix at Bits 1 / MinSize 8 (records of 8 to some 25 bytes), 10.5 bytes per record of N0
+    and a quarter more until wide_ok holds; and a copy of at least 64 KiB from byte 4,096 of the
+    main stream, whose chunks repeat records more than T back."""
+    t, n0 = wide_counts(cus)
+    size = int(10.5 * n0)
+    while True:
+        main = splitmix_array(0x51DE, size)
+        step = size // WIDE_EXCERPTS
+        cuts = [main[3000 + step * j:5000 + step * j] for j in range(WIDE_EXCERPTS)]
+        streams = cuts + [main, main[4096:4096 + max(64 << 10, size // 64)].copy()]
+        recs = oracle_records(O, table, streams, 1, 8)
+        first, uniq, _ = expected(recs)
+        if wide_ok(wide_facts(recs, first, uniq, t, WIDE_EXCERPTS), t, n0):
+            return (streams, 1, 8), recs
+        size += size // 4
+
+
+def wide_small(main):
+    """A small run at wide_run's parameters that shares content with it: a slice of the main
+    stream between two streams of its own."""
+    return [splitmix_array(0x51DF, 30_000), main[100_000:160_000].copy(),
+            splitmix_array(0x51E0, 20_001)], 1, 8
+
+
+def past_grid_refs(cus: int, repeats: int = 4096):
+    """Host refs for three bsg_refset_add calls on one set: (a, b, c, P).
+    a: n1 = T + 101 distinct random refs. b: the P - n1 fresh refs that bring the count to P, the
+    first doubling point >= n1, the first `repeats` of them leading; among the rest, at random
+    places, repeats of refs of a, and from entry T + repeats on a repeat of each leading ref (more
+    than T entries after its first occurrence). b is longer than T + 2 x repeats. c: one fresh
+    ref, the one that doubles a table of P keys."""
+    t, _ = wide_counts(cus)
+    n1 = t + 101
+    p = next(x for x in doubling_points(50) if x >= n1)
+    refs = random_refs(33, p + 1)
+    a, fresh, c = refs[:n1], refs[n1:p], refs[p:]
+    rng = np.random.default_rng(34)
+    f = len(fresh)
+    assert f >= repeats
+    nold = max(f // 4, t + 3 * repeats - f)
+    total = f + nold + repeats
+    b = np.zeros((total, 32), dtype=np.uint8)
+    b[:repeats] = fresh[:repeats]
+    rep_at = t + repeats + rng.choice(total - t - repeats, repeats, replace=False)
+    b[rep_at] = fresh[:repeats]
+    rest = np.setdiff1d(np.arange(repeats, total), rep_at)
+    old_at = rng.choice(rest, nold, replace=False)
+    b[old_at] = a[rng.integers(0, n1, nold)]
+    b[np.setdiff1d(rest, old_at)] = fresh[repeats:]
+    return a, b, c, p
+
+
+def same_ref(n: int) -> np.ndarray:
+    """n copies of one ref."""
+    return np.tile(random_refs(35, 1), (n, 1))
+
+
+def two_ref_stream(table, n: int):
+    """planting.level_stream's run of n level-0 chunks of 64 bytes at Bits 8 / MinSize 64: two
+    distinct windows in turn, so two distinct refs."""
+    import planting
+    return [planting.level_stream(table, 8, np.zeros(n, dtype=np.int64))], 8, 64
+
+
+WRAP_HEAD = 48   # refs whose first 8 bytes are 0xFF: their home is the last slot of any table
+WRAP_LOW = 48    # refs whose first 8 bytes are the integers 0 .. 47: their homes are slots 0 .. 47
+
+
+def wrap_base() -> np.ndarray:
+    """The 96 distinct refs of wrap_refs: 48 with an all-0xFF head (the first 16 differ only in
+    byte 31, the others anywhere in bytes 8 .. 31), then 48 with heads 0 .. 47, little-endian."""
+    rng = np.random.default_rng(58)
+    ff = np.tile(rng.integers(0, 256, 32, dtype=np.uint8), (WRAP_HEAD, 1))
+    ff[:16, 31] = np.arange(16) + 7
+    ff[16:, 8:] = rng.integers(0, 256, (WRAP_HEAD - 16, 24), dtype=np.uint8)
+    ff[:, :8] = 0xFF
+    lo = rng.integers(0, 256, (WRAP_LOW, 32), dtype=np.uint8)
+    lo[:, :8] = np.arange(WRAP_LOW, dtype="<u8").view(np.uint8).reshape(WRAP_LOW, 8)
+    return np.concatenate([ff, lo])
+
+
+def wrap_refs() -> np.ndarray:
+    """wrap_base with exact repeats of 15 refs of either kind, shuffled: the probe sequence of the
+    0xFF heads steps off the table's last slot and goes on from slot 0 through the homes of the
+    others, whatever the table's size."""
+    rng = np.random.default_rng(59)
+    base = wrap_base()
+    again = np.concatenate([base[rng.choice(WRAP_HEAD, 15, replace=False)],
+                            base[WRAP_HEAD + rng.choice(WRAP_LOW, 15, replace=False)]])
+    both = np.concatenate([base, again])
+    return both[rng.permutation(len(both))]
+
+
+def wrap_absent() -> np.ndarray:
+    """A ref with an all-0xFF head that wrap_base does not hold."""
+    r = wrap_base()[20].copy()
+    r[9] ^= 0x5A
+    return r
+
+
+WRAP_FILL = 8
+
+
+def end_fillers() -> np.ndarray:
+    """8 refs with the heads 2^64 - 2 .. 2^64 - 9: their homes are the 8 slots before the last
+    one of any table. With wrap_base in the table too, its last 9 slots are taken."""
+    r = random_refs(63, WRAP_FILL)
+    r[:, :8] = (~np.arange(1, WRAP_FILL + 1, dtype="<u8")).view(np.uint8).reshape(WRAP_FILL, 8)
+    return r
+
+
+def wrap_run():
+    """400 KB at Bits 6 / MinSize 64, about 3,000 records: SHA-256 refs cannot be planted, but of
+    so many some twenty have their home in the last 9 slots of a new set's table (near_end)."""
+    return [splitmix_array(71, 300_000), splitmix_array(72, 100_001)], 6, 64
+
+
+def near_end(recs, slots: int, k: int = WRAP_FILL + 1) -> np.ndarray:
+    """The indices of the records whose ref's home is one of the last k slots of `slots`."""
+    heads = np.ascontiguousarray(recs["ref"][:, :8]).view("<u8").ravel()
+    return np.flatnonzero((heads & np.uint64(slots - 1)) >= np.uint64(slots - k))
+
+
+def home(ref, slots: int) -> int:
+    """The slot a probe for `ref` starts at: its first 8 bytes, little-endian, modulo the size."""
+    return int.from_bytes(bytes(ref[:8]), "little") & (slots - 1)
+
+
+def probe_slots(refs, slots: int) -> dict:
+    """Plain linear probing of the distinct refs in list order into a table of `slots`:
+    {ref bytes: slot}."""
+    tab, where = [None] * slots, {}
+    for r in refs:
+        k = bytes(r)
+        if k in where:
+            continue
+        s = home(r, slots)
+        while tab[s] is not None:
+            s = (s + 1) % slots
+        tab[s] = k
+        where[k] = s
+    return where

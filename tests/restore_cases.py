@@ -250,6 +250,33 @@ def small_valid():
                 want=[np.frombuffer(b"".join(s), dtype=np.uint8) for s in streams])
 
 
+def wrap_pool():
+    """96 blobs of the distinct lengths 1 .. 96 labelled (verify off) with dedup_cases.wrap_base's
+    refs in a shuffled order, packed tight; each is named once by the records of two streams, in
+    another order. The pool index's probes for the 48 refs with an all-0xFF head start at the
+    table's last slot and go on from slot 0, through the homes of the other 48."""
+    rng = np.random.default_rng(61)
+    refs = DC.wrap_base()[rng.permutation(96)]
+    datas = [bytes(DC.splitmix_array(6100 + k, k + 1)) for k in range(96)]
+    offs = np.concatenate([[0], np.cumsum([len(d) for d in datas])])[:-1]
+    blobs = make_blobs(offs, [len(d) for d in datas], refs)
+    pool = np.frombuffer(b"".join(datas), dtype=np.uint8).copy()
+    order = rng.permutation(96)
+    pieces = [[int(k) for k in order[:50]], [int(k) for k in order[50:]]]
+    recs = make_recs([[datas[k] for k in s] for s in pieces])
+    recs["ref"] = refs[order]
+    streams = [np.frombuffer(b"".join(datas[k] for k in s), dtype=np.uint8) for s in pieces]
+    return case(pool, blobs, recs, [len(d) for d in streams], order=[1, 0], want=streams)
+
+
+def wrap_pool_absent(k: int = 37):
+    """wrap_pool with record k naming dedup_cases.wrap_absent: an all-0xFF head, in no blob."""
+    c = wrap_pool()
+    recs = c["recs"].copy()
+    recs[k]["ref"] = DC.wrap_absent()
+    return dict(c, recs=recs, want=None), k
+
+
 # ---- the device against the model (tests/test_gpu_restore*.py) ---------------------------------
 def run(gpu, eng, c, verify=None, pool_bytes=None, out_shift=0, pool_buf=None, expect=None):
     """One bsg_engine_restore of case `c` into a FILL-ed buffer with GUARD bytes at both ends;

@@ -629,9 +629,9 @@ CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
 
 
 def grid_caps() -> dict:
-    """What caps a launch of the walk's, the mark's and the restore's grid-stride kernels, read
-    from the source: engine_grid's workgroups per CU (of 256 threads), launch_walk_count's (of 4
-    waves, a node each) and the prefix sum's tile."""
+    """What caps a launch of the walk's, the mark's, the restore's and the dedup's grid-stride
+    kernels, read from the source: engine_grid's workgroups per CU (of 256 threads),
+    launch_walk_count's (of 4 waves, a node each) and the prefix sum's tile."""
     out = {}
 
     def one(fn, pattern, name):
