@@ -132,6 +132,30 @@ class GcInfo(ctypes.Structure):
 
 
 assert ctypes.sizeof(GcInfo) == 72
+POOL_CHUNKS = 1        # BSG_POOL_CHUNKS (Engine.pool_put)
+POOL_NODES = 2         # BSG_POOL_NODES
+
+
+class POOL_PUT_INFO(ctypes.Structure):
+    """bsg_pool_put_info (include/bsgpu.h)."""
+    _fields_ = [(k, ctypes.c_uint64) for k in
+                ("items", "added", "added_bytes", "known", "repeats", "first_blob", "need_bytes",
+                 "need_blobs")]
+
+    def as_dict(self) -> dict:
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+class PoolStats(ctypes.Structure):
+    """bsg_pool_stats (include/bsgpu.h)."""
+    _fields_ = [(k, ctypes.c_uint64) for k in
+                ("nblobs", "bytes", "cap_blobs", "cap_bytes", "pool_bytes")]
+
+    def as_dict(self) -> dict:
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+assert ctypes.sizeof(POOL_PUT_INFO) == 64 and ctypes.sizeof(PoolStats) == 40
 
 _lib = None
 
@@ -231,6 +255,18 @@ def lib() -> ctypes.CDLL:
         "bsg_engine_gc_compact": (ctypes.c_int, [vp, vp, ctypes.c_uint64, vp, ctypes.c_uint64,
                                                  ctypes.c_int, u64p]),
         "bsg_engine_gc_ms_debug": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_float)]),
+        "bsg_pool_new": (vp, [ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64,
+                              ctypes.POINTER(ctypes.c_int)]),
+        "bsg_pool_free": (None, [vp]),
+        "bsg_pool_stat": (ctypes.c_int, [vp, ctypes.POINTER(PoolStats)]),
+        "bsg_pool_bytes_device": (vp, [vp]),
+        "bsg_pool_table_device": (vp, [vp]),
+        "bsg_pool_copy_table": (ctypes.c_int, [vp, vp, ctypes.c_uint64, ctypes.c_uint64]),
+        "bsg_engine_pool_put": (ctypes.c_int, [vp, vp, ctypes.c_int,
+                                               ctypes.POINTER(POOL_PUT_INFO)]),
+        "bsg_pool_copy_where": (ctypes.c_int, [vp, vp, ctypes.c_uint64]),
+        "bsg_pool_where_device": (vp, [vp]),
+        "bsg_pool_put_ms_debug": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_float)]),
         "bsg_engine_pack_mode_debug": (ctypes.c_int, [vp, ctypes.c_int]),
         "bsg_engine_d2d_ms_debug": (ctypes.c_int, [vp, vp, vp, ctypes.c_uint64,
                                                    ctypes.POINTER(ctypes.c_float)]),
@@ -817,6 +853,18 @@ class Engine:
         return {"index": float(out[0]), "levels": float(out[1]), "offsets": float(out[2]),
                 "compact": float(out[3])}
 
+    def pool_put(self, pool: "Pool", chunks: bool = True, nodes: bool = True) -> dict:
+        """bsg_engine_pool_put: the last finished run's new chunks (its records) and new tree
+        nodes (needs trees()) appended to `pool`, on the device. Returns the call's
+        bsg_pool_put_info as a dict; raises BsgError (code, info) on any failure."""
+        flags = (POOL_CHUNKS if chunks else 0) | (POOL_NODES if nodes else 0)
+        info = POOL_PUT_INFO()
+        rc = lib().bsg_engine_pool_put(self.h, pool.h, flags, ctypes.byref(info))
+        if rc != BSG_OK:
+            raise BsgError(rc, "bsg_engine_pool_put", info.as_dict())
+        pool._items = int(info.items)
+        return info.as_dict()
+
     def dedup_ms(self) -> dict:
         """The last dedup() and pack_unique() calls in ms (test tooling; needs profile() on)."""
         out = (ctypes.c_float * 2)()
@@ -961,6 +1009,75 @@ class RefSet:
     def free(self) -> None:
         if self.h:
             lib().bsg_refset_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class Pool:
+    """bsg_pool: a pool of blobs that lives in device memory across runs (Engine.pool_put fills
+    it). Engine.walk, restore, restore_walk and gc_mark take it as
+    `pool.ptr, pool.table(), ..., pool_bytes=pool.pool_bytes`."""
+
+    def __init__(self, cap_bytes: int, cap_blobs: int, device: int = 0):
+        err = ctypes.c_int(0)
+        self.device, self._items = device, 0
+        self.h = lib().bsg_pool_new(device, cap_bytes, cap_blobs, ctypes.byref(err))
+        if not self.h:
+            raise BsgError(err.value, "bsg_pool_new")
+
+    def stat(self) -> dict:
+        st = PoolStats()
+        _check(lib().bsg_pool_stat(self.h, ctypes.byref(st)), "bsg_pool_stat")
+        return st.as_dict()
+
+    @property
+    def ptr(self) -> int:
+        """bsg_pool_bytes_device: the d_pool argument of walk / restore / gc."""
+        return lib().bsg_pool_bytes_device(self.h) or 0
+
+    @property
+    def pool_bytes(self) -> int:
+        return self.stat()["pool_bytes"]
+
+    def table(self, first: int = 0) -> np.ndarray:
+        """bsg_pool_copy_table: entries [first, nblobs) as POOL_BLOB_DTYPE."""
+        n = self.stat()["nblobs"] - first
+        out = np.zeros(max(n, 1), dtype=POOL_BLOB_DTYPE)
+        _check(lib().bsg_pool_copy_table(self.h, out.ctypes.data, first, max(n, 0)),
+               "bsg_pool_copy_table")
+        return out[:max(n, 0)]
+
+    def where(self) -> np.ndarray:
+        """bsg_pool_copy_where: the blob index of every item of the last successful put."""
+        out = np.zeros(max(self._items, 1), dtype=np.uint64)
+        _check(lib().bsg_pool_copy_where(self.h, out.ctypes.data, self._items),
+               "bsg_pool_copy_where")
+        return out[:self._items]
+
+    def to_host(self, n: int | None = None) -> np.ndarray:
+        """The pool's first n bytes (default: up to the end of its last blob)."""
+        n = self.stat()["bytes"] if n is None else n
+        out = np.empty(max(n, 1), dtype=np.uint8)
+        if n:
+            _check(lib().bsg_memcpy(self.device, out.ctypes.data, self.ptr, n, 1), "bsg_memcpy")
+        return out[:n]
+
+    def put_ms(self) -> dict:
+        """The last successful put's parts in ms (test tooling; the putting engine's profile()
+        must be on)."""
+        out = (ctypes.c_float * 4)()
+        _check(lib().bsg_pool_put_ms_debug(self.h, out), "bsg_pool_put_ms_debug")
+        return {"first": float(out[0]), "append": float(out[1]), "gather": float(out[2]),
+                "where": float(out[3])}
+
+    def free(self) -> None:
+        if self.h:
+            lib().bsg_pool_free(self.h)
             self.h = None
 
     def __del__(self):

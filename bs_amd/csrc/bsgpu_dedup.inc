@@ -28,10 +28,11 @@ __global__ __launch_bounds__(256) void k_dd_first(DedupArgs a) {
     }
     if (a.set_tab) {  // (a set's table is never full)
       const uint8_t* keys = a.set_keys;
+      const uint64_t ks = a.set_stride;
       const uint64_t c = ref_lookup(
           a.set_tab, a.set_mask, a.set_count, r,
-          [keys](uint64_t k) { return reinterpret_cast<const uint64_t*>(keys + 32 * k); }, a.hdr,
-          8, 16);
+          [keys, ks](uint64_t k) { return reinterpret_cast<const uint64_t*>(keys + ks * k); },
+          a.hdr, 8, 16);
       if (c != kDedupEmpty) f |= kDedupInSet;
     }
     a.first[i] = f;
@@ -44,8 +45,7 @@ struct DvNew {
 };
 struct DvNewBytes {
   __device__ uint64_t operator()(const DedupArgs& a, uint64_t i) const {
-    if (a.first[i] != i || !a.lens) return 0;
-    return *reinterpret_cast<const uint64_t*>(a.lens + i * a.len_stride);
+    return a.first[i] == i ? dd_len(a, i) : 0;
   }
 };
 

@@ -2,8 +2,8 @@
 // the multi-workgroup prefix sum, the table of indices by 32-byte ref (its insert kernel, its
 // read-only lookup, the index of a pool's blobs), the search for the segment that holds a
 // position and the per-thread gather of 16-byte output vectors from segments. Included from
-// bsgpu_kernels.hip before bsgpu_tree.inc, bsgpu_dedup.inc, bsgpu_restore.inc, bsgpu_walk.inc and
-// bsgpu_gc.inc, inside namespace bsg. DESIGN §4.6b.
+// bsgpu_kernels.hip before bsgpu_tree.inc, bsgpu_dedup.inc, bsgpu_restore.inc, bsgpu_walk.inc,
+// bsgpu_gc.inc and bsgpu_pool.inc, inside namespace bsg. DESIGN §4.6b.
 
 // workgroups of a grid-stride pass over `items`, 256 threads each
 static inline uint32_t engine_grid(uint64_t items, int num_cus) {
@@ -108,8 +108,18 @@ __device__ __forceinline__ void dd_error(DedupHdr* h, uint64_t code) {
   atomicOr(reinterpret_cast<unsigned long long*>(&h->error), (unsigned long long)code);
 }
 
+// item i's ref and length: items [0, n1) lie in refs / lens, the others in a second array with
+// the same strides (refs2; null: every item lies in the first)
 __device__ __forceinline__ const uint64_t* dd_ref(const DedupArgs& a, uint64_t i) {
+  if (a.refs2 && i >= a.n1)
+    return reinterpret_cast<const uint64_t*>(a.refs2 + (i - a.n1) * a.stride);
   return reinterpret_cast<const uint64_t*>(a.refs + i * a.stride);
+}
+
+__device__ __forceinline__ uint64_t dd_len(const DedupArgs& a, uint64_t i) {
+  if (a.refs2 && i >= a.n1)  // (a 4-byte length)
+    return *reinterpret_cast<const uint32_t*>(a.lens2 + (i - a.n1) * a.len_stride);
+  return a.lens ? *reinterpret_cast<const uint64_t*>(a.lens + i * a.len_stride) : 0;
 }
 
 __device__ __forceinline__ bool ref_eq(const uint64_t* x, const uint64_t* y) {

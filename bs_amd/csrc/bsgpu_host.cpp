@@ -1,7 +1,8 @@
 // bsgpu_host.cpp — libbsgpu host side: the C ABI declared in include/bsgpu.h. What it drives
 // lives in the headers included below, one per concern: host_mem.h (buffers, streams, knobs),
 // host_engine.h (the run pipeline; it includes the passes host_tree.h, host_dedup.h,
-// host_restore.h, host_walk.h and host_gc.h), host_stream.h (copy pool, streaming context), host_hasher.h.
+// host_restore.h, host_walk.h, host_gc.h and host_blobpool.h), host_stream.h (copy pool, streaming
+// context), host_hasher.h.
 //
 // A run = one launch sequence over a batch of stream segments (bsgpu_internal.h):
 //   k_start (descriptors in, counters zeroed) → k_scan (+ its exact pass) → prefix(strip counts) →
@@ -533,6 +534,109 @@ extern "C" int bsg_engine_gc_ms_debug(const bsg_engine* e, float out[4]) {
   if (!e->profile) return BSG_ESTATE;
   for (int i = 0; i < 3; ++i) out[i] = e->gc.ms[i];
   out[3] = e->gc.compact_ms;
+  return BSG_OK;
+}
+
+// ---- bsg_pool -----------------------------------------------------------------------------
+static_assert(sizeof(bsg_pool_put_info) == 64 && sizeof(bsg_pool_stats) == 40, "bsg_pool layouts");
+
+bsg_pool* bsg_pool_new(int device, uint64_t cap_bytes, uint64_t cap_blobs, int* err) {
+  int dummy;
+  if (!err) err = &dummy;
+  if (device < 0 || device >= bsg_device_count()) {
+    *err = BSG_ENODEV;
+    return nullptr;
+  }
+  bsg_pool* p = new (std::nothrow) bsg_pool();
+  if (!p) {
+    *err = BSG_ENOMEM;
+    return nullptr;
+  }
+  *err = herr(hipSetDevice(device));
+  if (*err == BSG_OK) *err = p->create(device, cap_bytes, cap_blobs);
+  if (*err == BSG_OK) return p;
+  (void)hipGetLastError();
+  delete p;
+  return nullptr;
+}
+
+void bsg_pool_free(bsg_pool* p) {
+  if (!p) return;
+  {
+    std::lock_guard<std::mutex> g(p->mu);  // a put on another thread ends first
+    hipSetDevice(p->dev);
+  }
+  delete p;
+}
+
+int bsg_pool_stat(const bsg_pool* p, bsg_pool_stats* out) {
+  if (!p || !out) return BSG_EINVAL;
+  std::lock_guard<std::mutex> g(const_cast<bsg_pool*>(p)->mu);
+  *out = bsg_pool_stats{p->nblobs, p->used, p->cap_blobs, p->cap_bytes, p->pool_bytes()};
+  return BSG_OK;
+}
+
+const uint8_t* bsg_pool_bytes_device(const bsg_pool* p) {
+  return p ? p->bytes.as<const uint8_t>() : nullptr;
+}
+
+const bsg_pool_blob* bsg_pool_table_device(const bsg_pool* p) {
+  return p ? p->table.as<const bsg_pool_blob>() : nullptr;
+}
+
+int bsg_pool_copy_table(bsg_pool* p, bsg_pool_blob* out, uint64_t first, uint64_t cap) {
+  if (!p || (!out && cap)) return BSG_EINVAL;
+  std::lock_guard<std::mutex> g(p->mu);
+  if (p->dead) return BSG_ESTATE;
+  if (first > p->nblobs) return BSG_EINVAL;
+  const uint64_t n = std::min<uint64_t>(cap, p->nblobs - first);
+  HCHECK(hipSetDevice(p->dev));
+  if (n)
+    HCHECK(hipMemcpy(out, p->table.as<PoolBlob>() + first, sizeof(PoolBlob) * n,
+                     hipMemcpyDeviceToHost));
+  return BSG_OK;
+}
+
+int bsg_pool_copy_where(bsg_pool* p, uint64_t* where, uint64_t cap) {
+  if (!p || (!where && cap)) return BSG_EINVAL;
+  std::lock_guard<std::mutex> g(p->mu);
+  if (p->dead || !p->put_done) return BSG_ESTATE;
+  const uint64_t n = std::min<uint64_t>(cap, p->nwhere);
+  HCHECK(hipSetDevice(p->dev));
+  if (n) HCHECK(hipMemcpy(where, p->where.p, 8 * n, hipMemcpyDeviceToHost));
+  return BSG_OK;
+}
+
+const uint64_t* bsg_pool_where_device(const bsg_pool* p) {
+  return p && p->put_done && !p->dead && p->nwhere ? p->where.as<const uint64_t>() : nullptr;
+}
+
+int bsg_engine_pool_put(bsg_engine* e, bsg_pool* p, int flags, bsg_pool_put_info* info) {
+  bsg_pool_put_info none{};
+  if (info) *info = none;
+  if (!e || !p || !flags || (flags & ~(BSG_POOL_CHUNKS | BSG_POOL_NODES)) || p->dev != e->dev)
+    return BSG_EINVAL;
+  std::lock_guard<std::mutex> g(p->mu);
+  // the run's input may not lie in the pool's own allocation: the append writes there
+  const uintptr_t s0 = reinterpret_cast<uintptr_t>(e->d_data), s1 = s0 + data_span(e->descs);
+  const uintptr_t p0 = reinterpret_cast<uintptr_t>(p->bytes.p), p1 = p0 + p->pool_bytes();
+  if (s0 < p1 && p0 < s1) return BSG_EINVAL;
+  const RunView v = e->view();
+  if (!v.usable || p->dead) return BSG_ESTATE;
+  const bool nodes = (flags & BSG_POOL_NODES) != 0;
+  if (nodes && !e->tree.current(e->run_done)) return BSG_ESTATE;
+  int rc = e->setdev();
+  if (rc) return rc;
+  return p->put(v, nodes ? &e->tree : nullptr, flags, info ? info : &none);
+}
+
+// Test and measurement tooling (not in bsgpu.h): the last successful bsg_engine_pool_put's parts
+// in ms (first occurrence and offsets, table append and index, gather, where[]), timed with HIP
+// events on the putting engine's stream when its bsg_engine_profile is on (else zeros).
+extern "C" int bsg_pool_put_ms_debug(bsg_pool* p, float out[4]) {
+  if (!p || !out) return BSG_EINVAL;
+  std::lock_guard<std::mutex> g(p->mu);
+  for (int i = 0; i < 4; ++i) out[i] = p->ms[i];
   return BSG_OK;
 }
 

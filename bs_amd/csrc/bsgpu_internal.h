@@ -299,4 +299,18 @@ struct GcHdr {                 // one mark's verdicts and totals, read back by t
 };
 static_assert(sizeof(GcHdr) % 16 == 0 && offsetof(GcHdr, zero) % 16 == 0, "GcHdr layout");
 
+// A run's new chunks and tree nodes appended to a pool that lives in device memory (bsg_pool,
+// bsg_engine_pool_put; bsgpu_pool.inc). The pool's index is the open-addressing table of blob
+// indices by ref that launch_ref_index builds for a caller's pool, kept and grown by inserts.
+constexpr uint32_t kPoolTile = 32768;         // output bytes per workgroup of the append's gather
+struct PoolHdr {               // one put's totals, read back by the host before the pool is written
+  DedupHdr dd;                 // the first-occurrence pass's header (dd.error: the bug guard)
+  uint64_t total16;            // the new blobs' lens, each rounded up to 16
+  uint64_t last_len;           // the last new blob's len
+  uint64_t known;              // items whose ref the pool held
+  uint64_t repeats;            // items that repeat an earlier item
+  uint8_t zero[16];            // the bytes of the padding
+};
+static_assert(sizeof(PoolHdr) % 16 == 0 && offsetof(PoolHdr, zero) % 16 == 0, "PoolHdr layout");
+
 }  // namespace bsg

@@ -2616,5 +2616,6 @@ hipError_t launch_sha_blobs(const BlobShaArgs& a, hipStream_t s, int num_cus) {
 #include "bsgpu_restore.inc"
 #include "bsgpu_walk.inc"
 #include "bsgpu_gc.inc"
+#include "bsgpu_pool.inc"
 
 }  // namespace bsg

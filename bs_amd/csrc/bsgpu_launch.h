@@ -208,16 +208,22 @@ hipError_t launch_tree_roots(const TreeArgs& a, hipStream_t s, int num_cus);
 // bsg_engine_dedup / bsg_refset_add (bsgpu_dedup.inc): the first occurrence of every 32-byte ref
 // among n items (a run's records, or refs a caller handed in) and in a set. Item i's ref is the
 // 32 bytes at refs + i * stride (8-byte aligned); its length the u64 at lens + i * len_stride
-// (null: 0). Nothing here writes the items.
+// (null: 0). With refs2, items [n1, n) lie in a second array with the same strides, item i at
+// index i - n1, its length the u32 at lens2 (bsg_engine_pool_put: the run's records, then its
+// tree nodes). Nothing here writes the items.
 struct DedupArgs {
   const uint8_t* refs;
   uint64_t stride;
   const uint8_t* lens;
   uint64_t len_stride;
   uint64_t n;
+  const uint8_t* refs2;      // (null: one array)
+  const uint8_t* lens2;
+  uint64_t n1;
   uint64_t* tab;             // [tab_mask + 1] the call's own table of item indices, kDedupEmpty-filled
   uint64_t tab_mask;
-  const uint8_t* set_keys;   // the set before the call (null: none): its keys, 32 bytes each,
+  const uint8_t* set_keys;   // the set before the call (null: none): its keys, the 32 bytes at
+  uint64_t set_stride;       //   set_keys + k * set_stride,
   const uint64_t* set_tab;   // and its table of key indices
   uint64_t set_mask;
   uint64_t set_count;
@@ -375,5 +381,40 @@ hipError_t launch_gc_status(const GcArgs& a, hipStream_t s, int num_cus);
 hipError_t launch_gc_missing(const GcArgs& a, hipStream_t s, int num_cus);
 hipError_t launch_gc_offsets(const GcArgs& a, hipStream_t s, int num_cus);
 hipError_t launch_gc_compact(const GcArgs& a, hipStream_t s);
+
+// bsg_engine_pool_put (bsgpu_pool.inc). d is the first-occurrence pass over the items (the run's
+// records, then with refs2 its tree nodes; d.set_* the pool's index before the call, d.hdr =
+// &hdr->dd). data .. arena_bytes say where an item's bytes lie, off16 and seg16 belong to the
+// call, bytes .. where to the pool. launch_pool_plan writes the call's buffers and the header only;
+// nnew and total16 are the header's, read back, before anything of the pool is written.
+struct PoolArgs {
+  DedupArgs d;
+  PoolHdr* hdr;
+  const uint8_t* data;       // the run's input and stream descriptors (records' bytes)
+  const StreamDesc* streams;
+  uint32_t nstreams;
+  const ChunkRec* rec;       // [d.n1]
+  const TreeNode* nodes;     // [d.n - d.n1]
+  const uint8_t* arena;      // the nodes' blobs
+  uint64_t arena_bytes;
+  uint64_t* off16;           // [d.n + 1] exclusive prefix of the new items' lens rounded up to 16
+  uint64_t* seg16;           // [nnew + 1] the same by rank: new blob k's bytes and padding
+  uint8_t* bytes;            // the pool
+  PoolBlob* table;
+  uint64_t* index;           // [index_mask + 1] blob indices by ref
+  uint64_t index_mask;
+  uint64_t nblobs;           // table entries before the call
+  uint64_t base;             // where the first new blob starts (a multiple of 16)
+  uint64_t nnew;
+  uint64_t total16;
+  uint64_t* where;           // [d.n]
+};
+// after launch_dedup(a.d): off16, seg16 and the header's totals
+hipError_t launch_pool_plan(const PoolArgs& a, hipStream_t s, int num_cus);
+// the new table entries and their index slots; the new blobs' bytes and padding
+hipError_t launch_pool_append(const PoolArgs& a, hipStream_t s, int num_cus);
+hipError_t launch_pool_gather(const PoolArgs& a, hipStream_t s);
+// where[i]: the blob that carries item i's ref, among nblobs + nnew
+hipError_t launch_pool_where(const PoolArgs& a, hipStream_t s, int num_cus);
 
 }  // namespace bsg

@@ -1,0 +1,177 @@
+// bsgpu_pool.inc — store/mem's Put for a pool that lives in device memory (bsg_pool,
+// bsg_engine_pool_put): the last run's new chunks and new tree nodes appended to the pool's bytes,
+// blob table and index. Included from bsgpu_kernels.hip after bsgpu_gc.inc, inside namespace bsg.
+// From bsgpu_engine_common.inc it takes the items' accessors (dd_ref, dd_len), the prefix sum
+// (launch_sum), pool_lookup, seg_find and gather_tile; from bsgpu_dedup.inc the first-occurrence
+// pass (launch_dedup, the pool's index in the place of a set's table) and set_insert. DESIGN §4.12.
+//
+// The items are the run's records and then its tree nodes, one index space (DedupArgs::refs2), so
+// launch_dedup's `first` and `rank` are the order of the append: the k-th new item becomes table
+// entry nblobs + k. Nothing before launch_pool_append writes the pool; the host reads the header
+// back in between and holds it to the pool's capacity. Every loop is bounded, every place read
+// from device memory is checked against a host-known bound before it forms an address, and every
+// atomic is a vector atomic on a device word.
+
+__device__ __forceinline__ uint64_t align16(uint64_t x) { return (x + 15) & ~15ull; }
+
+struct PvLen16 {
+  __device__ uint64_t operator()(const DedupArgs& a, uint64_t i) const {
+    return a.first[i] == i ? align16(dd_len(a, i)) : 0;
+  }
+};
+
+// ---- plan: the new blobs' places by rank, and the totals --------------------------------------
+__global__ __launch_bounds__(256) void k_pool_plan(PoolArgs a) {
+  const DedupArgs& d = a.d;
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  const uint64_t nu = d.rank[d.n];
+  unsigned long long known = 0, repeats = 0;
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < d.n; i += stride) {
+    const uint64_t f = d.first[i];
+    known += (f & kDedupInSet) != 0;
+    repeats += (f & ~kDedupInSet) != i;
+    if (f != i) continue;
+    const uint64_t k = d.rank[i];
+    if (k >= nu || nu > d.n) {
+      dd_error(d.hdr, 1 << 10);
+      continue;
+    }
+    a.seg16[k] = a.off16[i];
+    if (k + 1 == nu) a.hdr->last_len = dd_len(d, i);
+  }
+  if (known) atomicAdd(reinterpret_cast<unsigned long long*>(&a.hdr->known), known);
+  if (repeats) atomicAdd(reinterpret_cast<unsigned long long*>(&a.hdr->repeats), repeats);
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    if (nu <= d.n) a.seg16[nu] = a.off16[d.n];
+    else dd_error(d.hdr, 1 << 10);
+    a.hdr->total16 = a.off16[d.n];
+  }
+}
+
+// ---- append: table entries and index slots ----------------------------------------------------
+// The new refs are distinct from each other and from the pool's (launch_dedup's result), so an
+// entry claims the first free slot of its probe sequence and no key is compared, as k_set_add.
+__global__ __launch_bounds__(256) void k_pool_append(PoolArgs a) {
+  const DedupArgs& d = a.d;
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  SetArgs ix{};
+  ix.tab = a.index;
+  ix.mask = a.index_mask;
+  ix.hdr = d.hdr;
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < d.n; i += stride) {
+    if (d.first[i] != i) continue;
+    const uint64_t k = d.rank[i], len = dd_len(d, i), o = a.off16[i];
+    if (k >= a.nnew || o > a.total16 || align16(len) > a.total16 - o) {
+      dd_error(d.hdr, 1 << 11);
+      continue;
+    }
+    const uint64_t* r = dd_ref(d, i);
+    uint64_t* e = reinterpret_cast<uint64_t*>(a.table + a.nblobs + k);
+    e[0] = a.base + o;
+    e[1] = len;
+    for (int w = 0; w < 4; ++w) e[2 + w] = r[w];
+    set_insert(ix, r[0], a.nblobs + k);
+  }
+}
+
+// ---- gather: the new blobs' bytes -------------------------------------------------------------
+// item u's bytes: a record's in the run's input, a node's in the tree arena (null, and the error
+// flag, if the item is not sane or its len is not `len`)
+__device__ __forceinline__ const uint8_t* pool_src(const PoolArgs& a, uint64_t u, uint64_t len) {
+  const uint8_t* src = nullptr;
+  if (u < a.d.n1) {
+    const ChunkRec& r = a.rec[u];
+    const uint32_t s = r.stream;
+    if (s < a.nstreams && r.len == len && r.offset <= a.streams[s].len &&
+        len <= a.streams[s].len - r.offset)
+      src = a.data + a.streams[s].data_off + r.offset;
+  } else if (u < a.d.n) {
+    const TreeNode& t = a.nodes[u - a.d.n1];
+    if (t.blob_len == len && t.blob_off <= a.arena_bytes && len <= a.arena_bytes - t.blob_off)
+      src = a.arena + t.blob_off;
+  }
+  if (!src) dd_error(a.d.hdr, 1 << 12);
+  return src;
+}
+
+// Partitioned by output tiles of kPoolTile bytes, as k_pack and k_gc_compact. Segment k is new
+// blob k: its bytes at base + seg16[k], then the zero bytes (at most 15) up to seg16[k + 1].
+__global__ __launch_bounds__(256) void k_pool_gather(PoolArgs a) {
+  const uint64_t t0 = (uint64_t)blockIdx.x * kPoolTile;
+  if (t0 >= a.total16 || !a.nnew) return;
+  const uint64_t t1 = min(t0 + (uint64_t)kPoolTile, a.total16);
+  const auto off = [&a](uint64_t k) { return a.seg16[k]; };
+  __shared__ uint64_t seg[2];
+  if (threadIdx.x == 0) {
+    seg[0] = seg_find(0, a.nnew, t0, off);
+    seg[1] = seg_find(seg[0], a.nnew, t1 - 1, off);
+  }
+  __syncthreads();
+  const uint64_t k1 = seg[1];
+  uint64_t k = seg[0];
+  gather_tile<false>(a.bytes + a.base, t0, t1, a.total16, [&](uint64_t pos, GatherSeg* g) {
+    k = seg_find(k, k1 + 1, pos, off);
+    const uint64_t o = a.seg16[k], nx = a.seg16[k + 1], u = a.d.uniq[k];
+    g->src = nullptr;
+    if (pos < o || pos >= nx || nx > a.total16 || u >= a.d.n) {
+      dd_error(a.d.hdr, 1 << 12);
+      return false;
+    }
+    const uint64_t len = dd_len(a.d, u);
+    if (align16(len) != nx - o) {
+      dd_error(a.d.hdr, 1 << 12);
+      return false;
+    }
+    if (pos - o < len) {
+      g->src = pool_src(a, u, len);
+      g->b0 = o;
+      g->b1 = o + len;
+    } else {
+      g->src = a.hdr->zero;
+      g->b0 = o + len;
+      g->b1 = nx;
+    }
+    return g->src != nullptr;
+  });
+}
+
+// ---- where: every item's blob -----------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_pool_where(PoolArgs a) {
+  const DedupArgs& d = a.d;
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < d.n; i += stride) {
+    const uint64_t f =
+        pool_lookup(a.table, a.nblobs + a.nnew, a.index, a.index_mask, dd_ref(d, i), d.hdr);
+    if (f == kDedupEmpty) dd_error(d.hdr, 1 << 13);  // every item's ref is in the pool by now
+    a.where[i] = f;
+  }
+}
+
+// ---- launchers --------------------------------------------------------------------------------
+// a.d.n >= 1, after launch_dedup(a.d) on the same stream
+hipError_t launch_pool_plan(const PoolArgs& a, hipStream_t s, int num_cus) {
+  hipError_t e;
+  if ((e = launch_sum<PvLen16>(a.d, a.d.n, a.off16, s)) != hipSuccess) return e;
+  hipLaunchKernelGGL(k_pool_plan, dim3(engine_grid(a.d.n, num_cus)), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_pool_append(const PoolArgs& a, hipStream_t s, int num_cus) {
+  if (!a.nnew) return hipSuccess;
+  hipLaunchKernelGGL(k_pool_append, dim3(engine_grid(a.d.n, num_cus)), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_pool_gather(const PoolArgs& a, hipStream_t s) {
+  if (!a.total16) return hipSuccess;
+  const uint64_t tiles = (a.total16 + kPoolTile - 1) / kPoolTile;
+  if (tiles > 0x7fffffffull) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_pool_gather, dim3((uint32_t)tiles), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_pool_where(const PoolArgs& a, hipStream_t s, int num_cus) {
+  if (!a.d.n) return hipSuccess;
+  hipLaunchKernelGGL(k_pool_where, dim3(engine_grid(a.d.n, num_cus)), dim3(256), 0, s, a);
+  return hipGetLastError();
+}

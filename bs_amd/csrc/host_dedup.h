@@ -110,6 +110,7 @@ struct bsg_refset {
   // the set's part of a first-occurrence pass
   void lookup_args(DedupArgs* a) const {
     a->set_keys = keys.as<uint8_t>();
+    a->set_stride = 32;
     a->set_tab = tab.as<uint64_t>();
     a->set_mask = slots - 1;
     a->set_count = count.load();

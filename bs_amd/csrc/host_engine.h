@@ -87,6 +87,7 @@ int hash_batches(bsg_engine* owner, DevBuf& dbuf, uint64_t n, const uint8_t* dat
 #include "host_restore.h"
 #include "host_walk.h"
 #include "host_gc.h"
+#include "host_blobpool.h"
 
 struct bsg_engine {
   int dev = 0;
@@ -482,6 +483,7 @@ struct bsg_engine {
     int rc;
     run_done = false;
     dd.valid = false;  // a dedup result belongs to the run it was made from
+    tree.valid = false;  // ... and so does a tree (bsg_engine_pool_put reads both)
     if (early_open) {  // a failed run left second-stream work its engine stream never waited for
       HCHECK(hipStreamSynchronize(estream));
       early_open = false;
@@ -509,6 +511,7 @@ struct bsg_engine {
     int rc;
     run_done = false;
     dd.valid = false;  // a dedup result belongs to the run it was made from
+    tree.valid = false;  // ... and so does a tree (bsg_engine_pool_put reads both)
     const RunPlan pl = plan_hash();
     if ((rc = reserve(pl)) || (rc = run_start(pl, stream))) return rc;
     mark(0);

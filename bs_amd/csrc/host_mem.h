@@ -38,6 +38,14 @@ struct DevBuf {
     cap = want;
     return hipSuccess;
   }
+  // a buffer of a fixed size, allocated once and without headroom (a bsg_pool's bytes)
+  hipError_t exact(size_t bytes) {
+    release();
+    const hipError_t e = hipMalloc(&p, bytes ? bytes : 16);
+    if (e == hipSuccess) cap = bytes ? bytes : 16;
+    else p = nullptr;
+    return e;
+  }
   void release() {
     if (p) hipFree(p);
     p = nullptr;

@@ -494,6 +494,84 @@ const uint8_t*  bsg_engine_gc_live_device(const bsg_engine* eng);
 int bsg_engine_gc_compact(bsg_engine* eng, const uint8_t* d_pool, uint64_t pool_bytes,
                           uint8_t* d_out, uint64_t cap, int flags, uint64_t* out_bytes);
 
+/* ---- a pool that lives in device memory across runs: store/mem's Put for device-resident data ---- */
+/* store/mem keeps one blob per ref and reports `added` (store/mem/mem.go:62-77). A bsg_pool is
+ * that store in device memory: it owns its bytes, its blob table (bsg_pool_blob entries) and an
+ * index of blob indices by ref, and bsg_engine_pool_put appends the last run's new chunks and new
+ * tree nodes to it, on the device. Afterwards only a 48-byte table entry per new blob needs to
+ * cross the host link, and only when the caller asks for it.
+ * The pool. One allocation of cap_bytes rounded up to 16, plus BSG_READ_SLACK, zero-filled at
+ * creation, and a table of cap_blobs entries. Neither ever moves, so the device pointers below
+ * stay valid for the pool's life and a walk, restore or gc may hold them. The capacity is fixed and
+ * the pool only ever grows (no growth past the capacity, no delete; a pool is collected with
+ * bsg_engine_gc_mark / bsg_engine_gc_compact into another buffer). bsg_pool_new returns NULL with
+ * BSG_ENODEV (no such device) or BSG_ENOMEM in *err.
+ * Layout. Every blob starts at a multiple of 16 and the padding after it (at most 15 bytes) is
+ * zero, so the pool (bsg_pool_bytes_device, with pool_bytes of bsg_pool_stat and the table of
+ * bsg_pool_copy_table) is at all times a valid argument set for bsg_engine_walk,
+ * bsg_engine_restore, bsg_engine_restore_walk (with and without BSG_RESTORE_VERIFY) and
+ * bsg_engine_gc_mark. No two table entries carry one ref.
+ * Threading: a pool carries its own mutex, held for a whole call; engines on several threads may
+ * put into one pool, their calls serialize. */
+typedef struct bsg_pool bsg_pool;
+bsg_pool* bsg_pool_new(int device, uint64_t cap_bytes, uint64_t cap_blobs, int* err);
+void bsg_pool_free(bsg_pool* p);
+typedef struct bsg_pool_stats {
+  uint64_t nblobs, bytes;        /* table entries; the end of the last blob's last byte */
+  uint64_t cap_blobs, cap_bytes;
+  uint64_t pool_bytes;           /* what to pass as pool_bytes to walk / restore / gc */
+} bsg_pool_stats;
+int bsg_pool_stat(const bsg_pool* p, bsg_pool_stats* out);
+const uint8_t* bsg_pool_bytes_device(const bsg_pool* p); /* the d_pool argument */
+const bsg_pool_blob* bsg_pool_table_device(const bsg_pool* p);
+/* table[first .. first + n) to host memory, n = min(cap, nblobs - first). BSG_EINVAL for a null
+ * pool, first > nblobs or a null out with cap > 0; BSG_ESTATE for a dead pool. */
+int bsg_pool_copy_table(bsg_pool* p, bsg_pool_blob* out, uint64_t first, uint64_t cap);
+
+/* Appends to the pool, in this order, the items of the last finished bsg_engine_run: with
+ * BSG_POOL_CHUNKS its records, in the order of bsg_engine_chunks_device; then, with
+ * BSG_POOL_NODES, its tree's nodes, in the order of bsg_engine_tree_nodes_device. Item i is
+ * appended iff the pool does not hold its ref and no item j < i of this call carries it; a chunk
+ * and a node with equal bytes are one blob. The k-th appended item gets table entry
+ * first_blob + k = {off, len, ref} with off = align16(bytes before the call) + the sum of
+ * align16(len) over the items appended before it. Chunks are therefore stored before nodes and
+ * nodes in list order: a node is never in the table before what it points to
+ * (split/split.go:71-77). The table, the pool's bytes and where[] are a function of the sequence
+ * of puts alone, never of scheduling: two pools fed the same runs hold identical bytes.
+ * All or nothing. Which items are new and how many bytes and table entries they need is decided
+ * on the device and read back before anything of the pool is written. If need_bytes > cap_bytes
+ * or need_blobs > cap_blobs the call returns BSG_ENOMEM with info filled, and the pool's bytes,
+ * table, index, counters and where[] are unchanged (so is a put that cannot allocate its
+ * workspace). A device error during the append marks the pool dead: that call returns
+ * BSG_EDEVICE and every later call on the pool BSG_ESTATE, as for bsg_refset.
+ * Errors, in this order: BSG_EINVAL for a null engine or pool, flags 0 or unknown bits, a pool on
+ * another device than the engine, or a run whose input lies inside the pool's own allocation;
+ * BSG_ESTATE unless the engine's last enqueue was a bsg_engine_run that bsg_engine_finish
+ * completed (as bsg_engine_dedup), if BSG_POOL_NODES is set and no bsg_engine_trees result is
+ * current for that run, or if the pool is dead; then BSG_ENOMEM or BSG_EDEVICE as above.
+ * Synchronous, on the engine's stream. The caller keeps the run's input bytes valid and unchanged
+ * until the call returns. The engine's run is not touched: its records, bsg_engine_dedup result,
+ * tree, walk, restore and gc buffers stay as they are. info may be NULL. */
+#define BSG_POOL_CHUNKS 1 /* the run's records */
+#define BSG_POOL_NODES  2 /* the run's tree nodes (needs a current bsg_engine_trees result) */
+typedef struct bsg_pool_put_info {
+  uint64_t items;       /* records + nodes considered */
+  uint64_t added;       /* blobs appended */
+  uint64_t added_bytes; /* sum of their len (payload, without padding) */
+  uint64_t known;       /* items whose ref the pool held before the call */
+  uint64_t repeats;     /* items that repeat an earlier item of this call (such an item whose ref
+                           the pool held counts under known too) */
+  uint64_t first_blob;  /* nblobs before the call: the new blobs are [first_blob, first_blob + added) */
+  uint64_t need_bytes, need_blobs; /* bytes / nblobs the pool would have after the call (filled
+                                      on BSG_ENOMEM for want of capacity too) */
+} bsg_pool_put_info;
+int bsg_engine_pool_put(bsg_engine* eng, bsg_pool* pool, int flags, bsg_pool_put_info* info);
+/* where[i] = the pool blob index that carries item i's ref, for the items of the last successful
+ * put (up to cap of them to host memory). BSG_ESTATE before the first successful put (as the
+ * device pointer below is NULL, which it also is after a put without items) or on a dead pool. */
+int bsg_pool_copy_where(bsg_pool* p, uint64_t* where, uint64_t cap);
+const uint64_t* bsg_pool_where_device(const bsg_pool* p);
+
 /* Per-stage HIP event timing of later runs, and the last finished run's stage durations in
  * ms: [0] rolling scan (k_scan), [1] prefix/compact/select/chunks, [2] SHA-256 (k_sha, and the
  * early chains' tail). Timed on the engine's own stream. enable: 0 off, 1 every stage (four
