@@ -157,6 +157,18 @@ class PoolStats(ctypes.Structure):
 
 assert ctypes.sizeof(POOL_PUT_INFO) == 64 and ctypes.sizeof(PoolStats) == 40
 
+
+class PoolCollectInfo(ctypes.Structure):
+    """bsg_pool_collect_info (include/bsgpu.h)."""
+    _fields_ = [("gc", GcInfo), ("need_bytes", ctypes.c_uint64), ("need_blobs", ctypes.c_uint64)]
+
+    def as_dict(self) -> dict:
+        return {"gc": self.gc.as_dict(), "need_bytes": int(self.need_bytes),
+                "need_blobs": int(self.need_blobs)}
+
+
+assert ctypes.sizeof(PoolCollectInfo) == 88
+
 _lib = None
 
 
@@ -267,6 +279,17 @@ def lib() -> ctypes.CDLL:
         "bsg_pool_copy_where": (ctypes.c_int, [vp, vp, ctypes.c_uint64]),
         "bsg_pool_where_device": (vp, [vp]),
         "bsg_pool_put_ms_debug": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_float)]),
+        "bsg_pool_collect": (ctypes.c_int, [vp, vp, vp, vp, ctypes.c_uint64, ctypes.c_int, vp,
+                                            ctypes.POINTER(PoolCollectInfo)]),
+        "bsg_pool_copy_remap": (ctypes.c_int, [vp, vp, ctypes.c_uint64]),
+        "bsg_pool_remap_device": (vp, [vp]),
+        "bsg_pool_reset": (ctypes.c_int, [vp]),
+        "bsg_pool_walk": (ctypes.c_int, [vp, vp, vp, ctypes.c_uint32, ctypes.c_int, vp,
+                                         ctypes.POINTER(WalkInfo)]),
+        "bsg_pool_restore_walk": (ctypes.c_int, [vp, vp, vp, ctypes.c_uint64, u64p,
+                                                 ctypes.c_uint32, ctypes.c_int,
+                                                 ctypes.POINTER(RestoreInfo)]),
+        "bsg_pool_collect_ms_debug": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_float)]),
         "bsg_engine_pack_mode_debug": (ctypes.c_int, [vp, ctypes.c_int]),
         "bsg_engine_d2d_ms_debug": (ctypes.c_int, [vp, vp, vp, ctypes.c_uint64,
                                                    ctypes.POINTER(ctypes.c_float)]),
@@ -865,6 +888,56 @@ class Engine:
         pool._items = int(info.items)
         return info.as_dict()
 
+    def pool_collect(self, src: "Pool", dst: "Pool", roots, flags: int = 0):
+        """bsg_pool_collect: `src` marked from `roots` ([n, 32] uint8, or n * 32 bytes) where it
+        lies, its live blobs appended to the empty pool `dst`. Returns (rc, info, status): the
+        return code, the bsg_pool_collect_info as a dict and the per-Root status (int32); a
+        negative rc is returned, not raised. The mark is this engine's gc result afterwards
+        (copy_gc, gc_live_device, gc_compact on src.ptr)."""
+        roots = np.ascontiguousarray(np.frombuffer(roots, dtype=np.uint8)
+                                     if isinstance(roots, (bytes, bytearray)) else roots,
+                                     dtype=np.uint8).reshape(-1)
+        assert len(roots) % 32 == 0
+        nr = len(roots) // 32
+        status = np.zeros(max(nr, 1), dtype=np.int32)
+        info = PoolCollectInfo()
+        nsrc = src.stat()["nblobs"] if src is not None and src.h else 0
+        rc = lib().bsg_pool_collect(self.h, src.h if src is not None else None,
+                                    dst.h if dst is not None else None, roots.ctypes.data, nr,
+                                    flags, status.ctypes.data, ctypes.byref(info))
+        self._gc_nblobs, self._gc_nlive = nsrc, int(info.gc.nlive)
+        if rc == BSG_OK:
+            dst._nremap = nsrc
+        return rc, info.as_dict(), status[:nr]
+
+    def pool_walk(self, pool: "Pool", roots, flags: int = 0):
+        """bsg_pool_walk: walk() on a bsg_pool where it lies (its device table and index).
+        Returns (rc, info, status) as walk(); copy_walk() serves the result."""
+        roots = np.ascontiguousarray(np.frombuffer(roots, dtype=np.uint8)
+                                     if isinstance(roots, (bytes, bytearray)) else roots,
+                                     dtype=np.uint8).reshape(-1)
+        assert len(roots) % 32 == 0
+        ns = len(roots) // 32
+        status = np.zeros(max(ns, 1), dtype=np.int32)
+        info = WalkInfo()
+        rc = lib().bsg_pool_walk(self.h, pool.h if pool is not None else None, roots.ctypes.data,
+                                 ns, flags, status.ctypes.data, ctypes.byref(info))
+        self._walk_ns, self._walk_nrecs = ns, int(info.nrecs)
+        return rc, info.as_dict(), status[:ns]
+
+    def pool_restore_walk(self, pool: "Pool", out, out_off, verify: bool = False,
+                          out_cap: int | None = None):
+        """bsg_pool_restore_walk: restore_walk() on a bsg_pool where it lies. Returns (rc, info)
+        as restore_walk()."""
+        op = out.ptr if isinstance(out, DeviceBuffer) else out
+        out_cap = out.nbytes if out_cap is None else out_cap
+        oo = _u64(out_off)
+        info = RestoreInfo()
+        rc = lib().bsg_pool_restore_walk(self.h, pool.h if pool is not None else None, op, out_cap,
+                                         _p(oo, ctypes.c_uint64), len(oo),
+                                         RESTORE_VERIFY if verify else 0, ctypes.byref(info))
+        return rc, info.as_dict()
+
     def dedup_ms(self) -> dict:
         """The last dedup() and pack_unique() calls in ms (test tooling; needs profile() on)."""
         out = (ctypes.c_float * 2)()
@@ -1021,11 +1094,12 @@ class RefSet:
 class Pool:
     """bsg_pool: a pool of blobs that lives in device memory across runs (Engine.pool_put fills
     it). Engine.walk, restore, restore_walk and gc_mark take it as
-    `pool.ptr, pool.table(), ..., pool_bytes=pool.pool_bytes`."""
+    `pool.ptr, pool.table(), ..., pool_bytes=pool.pool_bytes`; Engine.pool_walk,
+    pool_restore_walk and pool_collect take it where it lies."""
 
     def __init__(self, cap_bytes: int, cap_blobs: int, device: int = 0):
         err = ctypes.c_int(0)
-        self.device, self._items = device, 0
+        self.device, self._items, self._nremap = device, 0, 0
         self.h = lib().bsg_pool_new(device, cap_bytes, cap_blobs, ctypes.byref(err))
         if not self.h:
             raise BsgError(err.value, "bsg_pool_new")
@@ -1066,6 +1140,35 @@ class Pool:
         if n:
             _check(lib().bsg_memcpy(self.device, out.ctypes.data, self.ptr, n, 1), "bsg_memcpy")
         return out[:n]
+
+    def remap(self) -> np.ndarray:
+        """bsg_pool_copy_remap: for every blob index of the source of the last successful collect
+        into this pool, its index here (NONE64 for a dead blob)."""
+        out = np.zeros(max(self._nremap, 1), dtype=np.uint64)
+        _check(lib().bsg_pool_copy_remap(self.h, out.ctypes.data, self._nremap),
+               "bsg_pool_copy_remap")
+        return out[:self._nremap]
+
+    def remap_device(self) -> int:
+        """bsg_pool_remap_device: remap's device address (0 without a collect)."""
+        return lib().bsg_pool_remap_device(self.h) or 0
+
+    def where_device(self) -> int:
+        """bsg_pool_where_device: where[]'s device address (0 without a put with items)."""
+        return lib().bsg_pool_where_device(self.h) or 0
+
+    def reset(self) -> None:
+        """bsg_pool_reset: the pool emptied for reuse, as new."""
+        _check(lib().bsg_pool_reset(self.h), "bsg_pool_reset")
+        self._items = self._nremap = 0
+
+    def collect_ms(self) -> float:
+        """The last successful collect into this pool: its k_pool_adopt in ms (test tooling; the
+        collecting engine's profile() must be on)."""
+        out = ctypes.c_float(0)
+        _check(lib().bsg_pool_collect_ms_debug(self.h, ctypes.byref(out)),
+               "bsg_pool_collect_ms_debug")
+        return float(out.value)
 
     def put_ms(self) -> dict:
         """The last successful put's parts in ms (test tooling; the putting engine's profile()

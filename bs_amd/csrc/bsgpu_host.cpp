@@ -630,6 +630,87 @@ int bsg_engine_pool_put(bsg_engine* e, bsg_pool* p, int flags, bsg_pool_put_info
   return p->put(v, nodes ? &e->tree : nullptr, flags, info ? info : &none);
 }
 
+// ---- a pool collected into a pool; the walk and the restore on a pool where it lies ---------
+static_assert(sizeof(bsg_pool_collect_info) == 88, "bsg_pool_collect_info layout");
+
+int bsg_pool_collect(bsg_engine* e, bsg_pool* src, bsg_pool* dst, const uint8_t* roots,
+                     uint64_t nroots, int flags, int32_t* status, bsg_pool_collect_info* info) {
+  bsg_pool_collect_info none{};
+  if (!info) info = &none;
+  *info = bsg_pool_collect_info{bsg_gc_info{UINT64_MAX, UINT64_MAX, 0, 0, 0, 0, 0, 0, 0, 0}, 0, 0};
+  if (!e || !src || !dst || src == dst || src->dev != e->dev || dst->dev != e->dev ||
+      (flags & ~BSG_GC_MISSING_LEAVES) || nroots > 0xffffffffull || (!roots && nroots))
+    return BSG_EINVAL;
+  // both pools for the whole call, taken together: A -> B beside B -> A cannot deadlock
+  std::unique_lock<std::mutex> gs(src->mu, std::defer_lock), gd(dst->mu, std::defer_lock);
+  std::lock(gs, gd);
+  if (src->dead || dst->dead || dst->nblobs || e->enqueued) return BSG_ESTATE;
+  int rc = e->setdev();
+  if (rc) return rc;
+  return dst->collect(e->view(), e->gc, *src, roots, nroots, flags, status, info);
+}
+
+int bsg_pool_copy_remap(bsg_pool* p, uint64_t* remap, uint64_t cap) {
+  if (!p || (!remap && cap)) return BSG_EINVAL;
+  std::lock_guard<std::mutex> g(p->mu);
+  if (p->dead || !p->collect_done) return BSG_ESTATE;
+  const uint64_t n = std::min<uint64_t>(cap, p->nremap);
+  HCHECK(hipSetDevice(p->dev));
+  if (n) HCHECK(hipMemcpy(remap, p->remap.p, 8 * n, hipMemcpyDeviceToHost));
+  return BSG_OK;
+}
+
+const uint64_t* bsg_pool_remap_device(const bsg_pool* p) {
+  return p && p->collect_done && !p->dead && p->nremap ? p->remap.as<const uint64_t>() : nullptr;
+}
+
+int bsg_pool_reset(bsg_pool* p) {
+  if (!p) return BSG_EINVAL;
+  std::lock_guard<std::mutex> g(p->mu);
+  HCHECK(hipSetDevice(p->dev));
+  return p->reset();
+}
+
+int bsg_pool_walk(bsg_engine* e, bsg_pool* p, const uint8_t* roots, uint32_t nstreams, int flags,
+                  int32_t* status, bsg_walk_info* info) {
+  if (info) *info = bsg_walk_info{UINT64_MAX, 0, 0, 0, 0, 0};
+  if (!e || !p || p->dev != e->dev) return BSG_EINVAL;
+  std::lock_guard<std::mutex> g(p->mu);
+  if (p->dead) return BSG_ESTATE;
+  int rc = e->setdev();
+  if (rc) return rc;
+  const PoolSrc ps = p->source();
+  return e->walk.run(e->view(), p->bytes.as<const uint8_t>(), p->pool_bytes(), nullptr, p->nblobs,
+                     roots, nstreams, flags, status, info, &ps);
+}
+
+int bsg_pool_restore_walk(bsg_engine* e, bsg_pool* p, uint8_t* d_out, uint64_t out_cap,
+                          const uint64_t* out_off, uint32_t nstreams, int flags,
+                          bsg_restore_info* info) {
+  if (info) *info = bsg_restore_info{UINT64_MAX, UINT64_MAX, 0, 0};
+  if (!e || !p || p->dev != e->dev) return BSG_EINVAL;
+  std::lock_guard<std::mutex> g(p->mu);
+  if (p->dead) return BSG_ESTATE;
+  if (!e->walk.valid) return BSG_ESTATE;
+  if (nstreams != e->walk.ns) return BSG_EINVAL;
+  int rc = e->setdev();
+  if (rc) return rc;
+  const PoolSrc ps = p->source();
+  return e->restore.run(e->view(), p->bytes.as<const uint8_t>(), p->pool_bytes(), nullptr,
+                        p->nblobs, nullptr, e->walk.nrecs, e->walk.recs.as<ChunkRec>(), d_out,
+                        out_cap, out_off, e->walk.sizes.data(), nstreams, flags, info, &ps);
+}
+
+// Test and measurement tooling (not in bsgpu.h): the last successful bsg_pool_collect into p: its
+// k_pool_adopt in ms, timed with HIP events on the collecting engine's stream when its
+// bsg_engine_profile is on (else zero). The mark and the gather are bsg_engine_gc_ms_debug's.
+extern "C" int bsg_pool_collect_ms_debug(bsg_pool* p, float* out) {
+  if (!p || !out) return BSG_EINVAL;
+  std::lock_guard<std::mutex> g(p->mu);
+  *out = p->adopt_ms;
+  return BSG_OK;
+}
+
 // Test and measurement tooling (not in bsgpu.h): the last successful bsg_engine_pool_put's parts
 // in ms (first occurrence and offsets, table append and index, gather, where[]), timed with HIP
 // events on the putting engine's stream when its bsg_engine_profile is on (else zeros).

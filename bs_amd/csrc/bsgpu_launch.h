@@ -293,8 +293,9 @@ struct RestoreArgs {
   uint8_t* out;
   RestoreHdr* hdr;
 };
-// the index of the pool's refs, every record resolved against it, the records' tiling checked
-hipError_t launch_restore_resolve(const RestoreArgs& a, hipStream_t s, int num_cus);
+// the index of the pool's refs (index: built here into a.tab; else a.tab holds it already), every
+// record resolved against it, the records' tiling checked
+hipError_t launch_restore_resolve(const RestoreArgs& a, bool index, hipStream_t s, int num_cus);
 // blobs [b0, b0 + n) as the descriptors of a hash run, and that run's records against their refs
 hipError_t launch_restore_descs(const RestoreArgs& a, uint64_t b0, uint32_t n, StreamDesc* d,
                                 hipStream_t s, int num_cus);
@@ -416,5 +417,25 @@ hipError_t launch_pool_append(const PoolArgs& a, hipStream_t s, int num_cus);
 hipError_t launch_pool_gather(const PoolArgs& a, hipStream_t s);
 // where[i]: the blob that carries item i's ref, among nblobs + nnew
 hipError_t launch_pool_where(const PoolArgs& a, hipStream_t s, int num_cus);
+
+// bsg_pool_collect (bsgpu_pool.inc): src .. noff16 are a finished mark of the source pool (GcArgs),
+// table .. remap belong to the destination, an empty pool whose capacity the host has held nlive
+// and total to. Live blob k becomes entry rank[k] = {noff16[k], len, ref} and enters the index;
+// remap[k] is that entry, or ~0 for a dead blob. The bytes are launch_gc_compact's.
+struct AdoptArgs {
+  const PoolBlob* src;       // [n] the source's table
+  uint64_t n;
+  const uint8_t* live;       // [n]
+  const uint64_t* rank;      // [n + 1]
+  const uint64_t* noff16;    // [n + 1]
+  uint64_t nlive;            // rank[n]
+  uint64_t total;            // the mark's end16
+  PoolBlob* table;           // [>= nlive]
+  uint64_t* index;           // [index_mask + 1] blob indices by ref, kDedupEmpty-filled
+  uint64_t index_mask;
+  uint64_t* remap;           // [n]
+  DedupHdr* hdr;
+};
+hipError_t launch_pool_adopt(const AdoptArgs& a, hipStream_t s, int num_cus);
 
 }  // namespace bsg

@@ -147,7 +147,41 @@ __global__ __launch_bounds__(256) void k_pool_where(PoolArgs a) {
   }
 }
 
+// ---- adopt: a marked pool's live blobs become an empty pool's entries (bsg_pool_collect) --------
+// Live blob k of the source becomes entry rank[k] at offset noff16[k], the place k_gc_compact
+// (coff = noff16) gives its bytes. The source holds no ref twice, so an entry claims the first free
+// slot of its probe sequence and no key is compared, as k_pool_append. DESIGN §4.13.
+__global__ __launch_bounds__(256) void k_pool_adopt(AdoptArgs a) {
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  SetArgs ix{};
+  ix.tab = a.index;
+  ix.mask = a.index_mask;
+  ix.hdr = a.hdr;
+  for (uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; k < a.n; k += stride) {
+    a.remap[k] = ~0ull;
+    if (!a.live[k]) continue;
+    const uint64_t j = a.rank[k], len = a.src[k].len, o = a.noff16[k];
+    if (j >= a.nlive || o % 16 || o > a.total || len > a.total - o) {
+      dd_error(a.hdr, 1 << 14);
+      continue;
+    }
+    const uint64_t* r = reinterpret_cast<const uint64_t*>(a.src[k].ref);
+    uint64_t* e = reinterpret_cast<uint64_t*>(a.table + j);
+    e[0] = o;
+    e[1] = len;
+    for (int w = 0; w < 4; ++w) e[2 + w] = r[w];
+    set_insert(ix, r[0], j);
+    a.remap[k] = j;
+  }
+}
+
 // ---- launchers --------------------------------------------------------------------------------
+hipError_t launch_pool_adopt(const AdoptArgs& a, hipStream_t s, int num_cus) {
+  if (!a.n) return hipSuccess;
+  hipLaunchKernelGGL(k_pool_adopt, dim3(engine_grid(a.n, num_cus)), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+
 // a.d.n >= 1, after launch_dedup(a.d) on the same stream
 hipError_t launch_pool_plan(const PoolArgs& a, hipStream_t s, int num_cus) {
   hipError_t e;

@@ -183,10 +183,12 @@ __global__ __launch_bounds__(256) void k_rs_scatter(RestoreArgs a) {
 }
 
 // ---- launchers ---------------------------------------------------------------------------------
-hipError_t launch_restore_resolve(const RestoreArgs& a, hipStream_t s, int num_cus) {
-  const hipError_t e =
-      launch_ref_index(a.blobs, a.nblobs, a.tab, a.tab_mask, &a.hdr->dd, s, num_cus);
-  if (e != hipSuccess) return e;
+hipError_t launch_restore_resolve(const RestoreArgs& a, bool index, hipStream_t s, int num_cus) {
+  if (index) {  // (false: a.tab is a bsg_pool's own index)
+    const hipError_t e =
+        launch_ref_index(a.blobs, a.nblobs, a.tab, a.tab_mask, &a.hdr->dd, s, num_cus);
+    if (e != hipSuccess) return e;
+  }
   if (a.nrec) {
     const uint32_t g = engine_grid(a.nrec, num_cus);
     hipLaunchKernelGGL(k_rs_resolve, dim3(g), dim3(256), 0, s, a);

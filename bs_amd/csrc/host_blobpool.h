@@ -1,6 +1,7 @@
-// host_blobpool.h — bsg_pool and bsg_engine_pool_put: a pool of blobs that lives in device memory
-// across runs, and the last finished run's new chunks and tree nodes appended to it (included by
-// host_engine.h). Not host_pool.h (the copy threads) and not DevicePool (idle engines).
+// host_blobpool.h — bsg_pool, bsg_engine_pool_put and bsg_pool_collect: a pool of blobs that lives
+// in device memory across runs, the last finished run's new chunks and tree nodes appended to it,
+// and a pool's live blobs collected into an empty pool (included by host_engine.h). Not
+// host_pool.h (the copy threads) and not DevicePool (idle engines).
 #pragma once
 
 // The pool owns its bytes, its blob table and its index of blob indices by ref, none of which
@@ -14,15 +15,20 @@ struct bsg_pool {
   uint64_t cap_bytes = 0, cap_blobs = 0;
   uint64_t slots = 0;               // of index (a power of two)
   uint64_t nblobs = 0, used = 0;    // table entries; the end of the last blob's last byte
+  uint64_t blob_bytes = 0;          // the blobs' lens, summed
   bool dead = false;                // a device error during an append: BSG_ESTATE from then on
   DevBuf where;                     // the last successful put's items -> blob indices
   uint64_t nwhere = 0;
   bool put_done = false;
+  DevBuf remap;                     // the last collect into this pool: the source's blob indices ->
+  uint64_t nremap = 0;              //   this pool's, ~0 for a dead blob
+  bool collect_done = false;
   DevBuf off16, seg16, hdr;         // a put's own buffers
   PinBuf h_hdr;
   DedupWork work;
   Marks marks;                      // profile
   float ms[4] = {0, 0, 0, 0};       // profile: first occurrence + offsets, append, gather, where
+  float adopt_ms = 0;               // profile: the last collect's k_pool_adopt
 
   static uint64_t pad16(uint64_t x) { return (x + 15) & ~15ull; }
   uint64_t pool_bytes() const { return pad16(cap_bytes) + kReadSlack; }
@@ -159,11 +165,95 @@ struct bsg_pool {
     put_done = true;
     nblobs = out.need_blobs;
     used = out.need_bytes;
+    blob_bytes += out.added_bytes;
     for (int i = 0; i < 4; ++i) ms[i] = 0.f;
     if (v.profile) {
       ms[0] = marks.ms(0, 1);
       for (int i = 1; i < 4; ++i) ms[i] = marks.ms(i + 1, i + 2);
     }
+    return BSG_OK;
+  }
+
+  // the table and the index where they lie, for a walk, a restore or a mark (the caller holds mu)
+  PoolSrc source() const {
+    return PoolSrc{table.as<const PoolBlob>(), index.as<uint64_t>(), slots - 1, used, blob_bytes};
+  }
+
+  // bsg_pool_collect: `src` marked from the Roots by gc (the engine's, whose current result the
+  // mark becomes), then its live blobs appended to this empty pool. The mark, the offsets and the
+  // readback of the totals write gc's buffers only; nothing of this pool is written before they
+  // have been held to its capacity. (The caller holds both mutexes and has checked the states.)
+  int collect(const RunView& v, GcWork& gc, const bsg_pool& src, const uint8_t* roots,
+              uint64_t nroots, int flags, int32_t* status, bsg_pool_collect_info* info) {
+    const hipStream_t s = v.stream;
+    const PoolSrc ps = src.source();
+    const uint64_t n = src.nblobs;
+    int rc = gc.mark(v, src.bytes.as<const uint8_t>(), src.pool_bytes(), nullptr, n, roots, nroots,
+                     flags, status, &info->gc, &ps);
+    if (rc) return rc;
+    info->need_blobs = gc.nlive;
+    info->need_bytes = gc.end16;
+    if (gc.nlive > cap_blobs || gc.end16 > cap_bytes) return BSG_ENOMEM;
+    DevBuf map;  // (a failed collect keeps the last one's remap)
+    MCHECK(map.ensure(8 * n));
+
+    AdoptArgs a{};
+    a.src = ps.table;
+    a.n = n;
+    a.live = gc.live.as<const uint8_t>();
+    a.rank = gc.rank.as<const uint64_t>();
+    a.noff16 = gc.noff16.as<const uint64_t>();
+    a.nlive = gc.nlive;
+    a.total = gc.end16;
+    a.table = table.as<PoolBlob>();
+    a.index = index.as<uint64_t>();
+    a.index_mask = slots - 1;
+    a.remap = map.as<uint64_t>();
+    a.hdr = &hdr.as<PoolHdr>()->dd;
+    if (v.profile) marks.record(6, s);
+    hipError_t e = hipMemsetAsync(hdr.p, 0, sizeof(PoolHdr), s);
+    if (e == hipSuccess) e = dbg("launch_pool_adopt", s, launch_pool_adopt(a, s, v.num_cus));
+    if (v.profile) marks.record(7, s);
+    PoolHdr h;
+    rc = e == hipSuccess ? readback(s, &h) : BSG_EDEVICE;
+    uint64_t wrote = 0;
+    if (!rc)
+      rc = gc.compact(v, src.bytes.as<const uint8_t>(), src.pool_bytes(), bytes.as<uint8_t>(),
+                      cap_bytes, BSG_GC_ALIGN16, &wrote);
+    if (rc || wrote != gc.end16) {  // the table, the index or the bytes may be half written
+      (void)hipGetLastError();
+      (void)hipStreamSynchronize(s);
+      dead = true;
+      return BSG_EDEVICE;
+    }
+    remap = std::move(map);
+    nremap = n;
+    collect_done = true;
+    nblobs = gc.nlive;
+    used = gc.end16;
+    blob_bytes = info->gc.live_bytes;
+    adopt_ms = v.profile ? marks.ms(6, 7) : 0.f;
+    return BSG_OK;
+  }
+
+  // bsg_pool_reset: a new pool of the same capacity in the place of this one, dead or not. What a
+  // put or a collect may have written is refilled: the index, the table's entries and the bytes in
+  // use, or all of both after a device error. (The caller holds mu.)
+  int reset() {
+    const uint64_t nb = dead ? pool_bytes() : pad16(used);
+    const uint64_t nt = dead ? table.cap : sizeof(PoolBlob) * nblobs;
+    if (nb) HCHECK(hipMemset(bytes.p, 0, nb));
+    if (nt) HCHECK(hipMemset(table.p, 0, nt));
+    HCHECK(hipMemset(index.p, 0xFF, 8 * slots));
+    HCHECK(hipStreamSynchronize(nullptr));  // (as create)
+    where.release();
+    remap.release();
+    nwhere = nremap = 0;
+    put_done = collect_done = false;
+    nblobs = used = blob_bytes = 0;
+    for (float& m : ms) m = 0.f;
+    adopt_ms = 0.f;
+    dead = false;
     return BSG_OK;
   }
 };

@@ -12,9 +12,13 @@ struct GcWork {
   RefTable tab;
   std::vector<WalkLevel> lv;  // (prec unused)
   PinBuf h_in, h_out;
-  std::vector<PoolBlob> blobs;  // the marked pool's table
+  std::vector<PoolBlob> blobs;  // the marked pool's table (empty if it is a bsg_pool's: d_blobs)
   const uint8_t* d_pool = nullptr;
-  uint64_t pool_bytes = 0, nblobs = 0, o_blobs = 0;
+  const PoolBlob* d_blobs = nullptr;  // the table and the index the mark read: its own upload and
+  uint64_t* d_tab = nullptr;          // `tab`, or a bsg_pool's
+  uint64_t d_mask = 0;
+  bool from_pool = false;
+  uint64_t pool_bytes = 0, nblobs = 0;
   uint64_t nlive = 0, end = 0, end16 = 0;
   bool valid = false;
   Marks marks;              // profile
@@ -29,11 +33,11 @@ struct GcWork {
     GcArgs a{};
     a.w.pool = d_pool;
     a.w.pool_bytes = pool_bytes;
-    a.w.blobs = reinterpret_cast<const PoolBlob*>(in.as<uint8_t>() + o_blobs);
+    a.w.blobs = d_blobs;
     a.w.nblobs = nblobs;
     a.w.ns = 1;  // the count pass's one stream: its size and status go to the header's spare words
-    a.w.tab = tab.p();
-    a.w.tab_mask = tab.mask();
+    a.w.tab = d_tab;
+    a.w.tab_mask = d_mask;
     a.g = in.as<GcHdr>();
     a.w.hdr = &a.g->w;
     a.w.sizes = &a.g->size0;
@@ -52,24 +56,26 @@ struct GcWork {
 
   // The host checks its own arrays; every node is validated on the device, level by level, with
   // one small readback per level for the next frontier's size. Nothing is published before the
-  // verdict is in.
+  // verdict is in. With `ps` the table and the index are a bsg_pool's, read where they lie: no
+  // table is uploaded, no index built, and the pool's invariant stands for the loop over the blobs.
   int mark(const RunView& v, const uint8_t* pool, uint64_t pbytes, const bsg_pool_blob* tbl,
            uint64_t n_blobs, const uint8_t* roots, uint64_t nroots, int flags, int32_t* status,
-           bsg_gc_info* info) {
+           bsg_gc_info* info, const PoolSrc* ps = nullptr) {
     const hipStream_t stream = v.stream;
     auto stamp = [&](size_t i) { v.profile ? marks.record(i, stream) : void(); };
     valid = false;
     if ((flags & ~BSG_GC_MISSING_LEAVES) || nroots > 0xffffffffull) return BSG_EINVAL;
-    if ((!pool && pbytes) || (!tbl && n_blobs) || (!roots && nroots)) return BSG_EINVAL;
+    if ((!pool && pbytes) || (!tbl && !ps && n_blobs) || (!roots && nroots)) return BSG_EINVAL;
     const uintptr_t p0 = reinterpret_cast<uintptr_t>(pool);
     if (p0 + pbytes < p0) return BSG_EINVAL;
-    for (uint64_t k = 0; k < n_blobs; ++k)
+    for (uint64_t k = 0; k < n_blobs && !ps; ++k)
       if (tbl[k].off > pbytes || tbl[k].len > pbytes - tbl[k].off) return BSG_EINVAL;
+    if (ps && ps->used > pbytes) return BSG_EINVAL;
 
-    // the input block: header | blobs | Roots (the first comes back)
+    // the input block: header | blobs (the call's own table only) | Roots (the first comes back)
     auto pad16 = [](uint64_t x) { return (x + 15) & ~15ull; };
     const uint64_t ob = sizeof(GcHdr);
-    const uint64_t o_roots = ob + pad16(sizeof(PoolBlob) * n_blobs);
+    const uint64_t o_roots = ob + (ps ? 0 : pad16(sizeof(PoolBlob) * n_blobs));
     const uint64_t in_bytes = o_roots + pad16(32 * nroots);
     MCHECK(h_in.ensure(in_bytes));
     MCHECK(h_out.ensure(std::max<uint64_t>(sizeof(GcHdr) + 24, 4 * nroots)));
@@ -77,12 +83,12 @@ struct GcWork {
     GcHdr h{};
     h.bad_form = h.bad_miss = ~0ull;
     std::memcpy(hin, &h, sizeof h);
-    if (n_blobs) std::memcpy(hin + ob, tbl, sizeof(PoolBlob) * n_blobs);
+    if (n_blobs && !ps) std::memcpy(hin + ob, tbl, sizeof(PoolBlob) * n_blobs);
     if (nroots) std::memcpy(hin + o_roots, roots, 32 * nroots);
 
     lv.resize(kWalkMaxDepth + 2);
     MCHECK(in.ensure(in_bytes));
-    MCHECK(tab.reserve(n_blobs));
+    if (!ps) MCHECK(tab.reserve(n_blobs));
     MCHECK(live.ensure(n_blobs));
     MCHECK(state.ensure(4 * n_blobs));
     MCHECK(rblob.ensure(8 * nroots));
@@ -95,7 +101,10 @@ struct GcWork {
     d_pool = pool;
     pool_bytes = pbytes;
     nblobs = n_blobs;
-    o_blobs = ob;
+    from_pool = ps != nullptr;
+    d_blobs = ps ? ps->table : reinterpret_cast<const PoolBlob*>(in.as<uint8_t>() + ob);
+    d_tab = ps ? ps->index : tab.p();
+    d_mask = ps ? ps->mask : tab.mask();
     GcArgs base = base_args();
     base.roots = in.as<uint8_t>() + o_roots;
     base.nroots = nroots;
@@ -116,14 +125,15 @@ struct GcWork {
     int rc;
     stamp(0);
     HCHECK(hipMemcpyAsync(in.p, hin, in_bytes, hipMemcpyHostToDevice, stream));
-    HCHECK(tab.clear(stream));
+    if (!ps) HCHECK(tab.clear(stream));
     if (n_blobs) {
       HCHECK(hipMemsetAsync(live.p, 0, n_blobs, stream));
       HCHECK(hipMemsetAsync(state.p, 0, 4 * n_blobs, stream));
     }
-    HCHECK(dbg("launch_ref_index", stream,
-               launch_ref_index(base.w.blobs, n_blobs, base.w.tab, base.w.tab_mask,
-                                &base.w.hdr->dd, stream, v.num_cus)));
+    if (!ps)
+      HCHECK(dbg("launch_ref_index", stream,
+                 launch_ref_index(base.w.blobs, n_blobs, base.w.tab, base.w.tab_mask,
+                                  &base.w.hdr->dd, stream, v.num_cus)));
     {
       GcArgs a = base;
       a.w.items = lv[0].items.as<WalkItem>();
@@ -214,9 +224,11 @@ struct GcWork {
     ms[2] = v.profile ? marks.ms(3, 4) : 0.f;
     if (tot[0] > n_blobs || h.end > tot[1] || h.end16 > tot[2]) return BSG_EDEVICE;
 
-    blobs.assign(reinterpret_cast<const PoolBlob*>(tbl),
-                 reinterpret_cast<const PoolBlob*>(tbl) + n_blobs);
-    uint64_t all_bytes = 0;
+    blobs.clear();
+    if (!ps)
+      blobs.assign(reinterpret_cast<const PoolBlob*>(tbl),
+                   reinterpret_cast<const PoolBlob*>(tbl) + n_blobs);
+    uint64_t all_bytes = ps ? ps->blob_bytes : 0;
     for (const PoolBlob& b : blobs) all_bytes += b.len;
     nlive = tot[0];
     end = h.end;
@@ -243,6 +255,11 @@ struct GcWork {
     const uint64_t nl = std::min(cap_live, nblobs);
     if (out_live && nl) std::memcpy(out_live, lv8.data(), nl);
     if (!table || !cap_table) return BSG_OK;
+    if (from_pool) {  // the marked entries, from the pool (they never change while it lives)
+      blobs.resize(nblobs);
+      HCHECK(hipMemcpy(blobs.data(), d_blobs, sizeof(PoolBlob) * nblobs, hipMemcpyDeviceToHost));
+      from_pool = false;
+    }
     std::vector<uint64_t> off(nblobs + 1);
     HCHECK(hipMemcpy(off.data(), (flags & BSG_GC_ALIGN16) ? noff16.p : noff.p, 8 * (nblobs + 1),
                      hipMemcpyDeviceToHost));

@@ -395,6 +395,17 @@ struct RefTable {
   uint64_t mask() const { return slots - 1; }
 };
 
+// A bsg_pool's table and index where they lie on the device, for a pass (walk, restore, mark) that
+// takes them in the place of a table it uploads and an index it builds. The pool's own invariant
+// stands for the host's loop over the blobs: every blob lies in [0, used) at a multiple of 16.
+struct PoolSrc {
+  const PoolBlob* table;
+  uint64_t* index;      // (read only)
+  uint64_t mask;
+  uint64_t used;        // the end of the last blob's last byte
+  uint64_t blob_bytes;  // the blobs' lens, summed
+};
+
 // One HIP event, created at first use and destroyed with its owner (move-only).
 struct Event {
   hipEvent_t e = nullptr;

@@ -21,17 +21,18 @@ struct RestoreWork {
   // the blobs' bounds); the records, in their hundreds of thousands, are resolved and checked
   // on the device. Nothing is written to d_out before the header has come back clean.
   // The records come from the host (recs, uploaded with the rest) or, with d_recs, are read where
-  // they lie on the device (bsg_engine_restore_walk).
+  // they lie on the device (bsg_engine_restore_walk). With `ps` the table and the index are a
+  // bsg_pool's, read where they lie (bsg_pool_restore_walk).
   int run(const RunView& v, const uint8_t* d_pool, uint64_t pool_bytes,
           const bsg_pool_blob* blobs, uint64_t nblobs, const bsg_chunk* recs, uint64_t nrecs,
           const ChunkRec* d_recs, uint8_t* d_out, uint64_t out_cap, const uint64_t* out_off, const uint64_t* out_len,
-          uint32_t ns, int flags, bsg_restore_info* info) {
+          uint32_t ns, int flags, bsg_restore_info* info, const PoolSrc* ps = nullptr) {
     const hipStream_t stream = v.stream;
     auto mark = [&](size_t i) { v.profile ? marks.record(i, stream) : void(); };
     auto elapsed = [&](size_t i, size_t j) { return v.profile ? marks.ms(i, j) : 0.f; };
     const bool verify = (flags & BSG_RESTORE_VERIFY) != 0;
     if (flags & ~BSG_RESTORE_VERIFY) return BSG_EINVAL;
-    if ((!d_pool && pool_bytes) || (!blobs && nblobs) || (!recs && !d_recs && nrecs) || (!d_out && out_cap) ||
+    if ((!d_pool && pool_bytes) || (!blobs && !ps && nblobs) || (!recs && !d_recs && nrecs) || (!d_out && out_cap) ||
         (ns && (!out_off || !out_len)))
       return BSG_EINVAL;
     if (reinterpret_cast<uintptr_t>(d_out) % 16 != 0) return BSG_EINVAL;
@@ -42,7 +43,7 @@ struct RestoreWork {
     // the input block: header | blobs | records | out_off | out_len | tile prefix
     auto pad16 = [](uint64_t v) { return (v + 15) & ~15ull; };
     const uint64_t o_blobs = sizeof(RestoreHdr);
-    const uint64_t o_recs = o_blobs + pad16(sizeof(PoolBlob) * nblobs);
+    const uint64_t o_recs = o_blobs + (ps ? 0 : pad16(sizeof(PoolBlob) * nblobs));
     const uint64_t o_off = o_recs + (d_recs ? 0 : pad16(sizeof(ChunkRec) * nrecs));
     const uint64_t o_len = o_off + pad16(8ull * ns);
     const uint64_t o_tpre = o_len + pad16(8ull * ns);
@@ -72,7 +73,12 @@ struct RestoreWork {
     if (tiles > 0x7fffffffull) return BSG_EINVAL;
 
     uint64_t blob_bytes = 0, blob_hi = 0;
-    for (uint64_t k = 0; k < nblobs; ++k) {
+    if (ps) {  // the pool's invariant: every blob at a multiple of 16 in [0, used)
+      if (ps->used > pool_bytes || (verify && ps->used >= (1ull << 40))) return BSG_EINVAL;
+      blob_bytes = ps->blob_bytes;
+      blob_hi = ps->used;
+    }
+    for (uint64_t k = 0; k < nblobs && !ps; ++k) {
       if (blobs[k].off > pool_bytes || blobs[k].len > pool_bytes - blobs[k].off) return BSG_EINVAL;
       if (verify && (blobs[k].off % 16 != 0 || blobs[k].len >= (1ull << 40))) return BSG_EINVAL;
       blob_bytes += blobs[k].len;
@@ -84,7 +90,7 @@ struct RestoreWork {
     RestoreHdr* h0 = reinterpret_cast<RestoreHdr*>(hin);
     *h0 = RestoreHdr{};
     h0->missing = h0->mismatch = h0->bad_blob = ~0ull;
-    if (nblobs) std::memcpy(hin + o_blobs, blobs, sizeof(PoolBlob) * nblobs);
+    if (nblobs && !ps) std::memcpy(hin + o_blobs, blobs, sizeof(PoolBlob) * nblobs);
     if (nrecs && !d_recs) std::memcpy(hin + o_recs, recs, sizeof(ChunkRec) * nrecs);
     if (ns) {
       std::memcpy(hin + o_off, out_off, 8ull * ns);
@@ -93,13 +99,13 @@ struct RestoreWork {
 
     const uint64_t ns1 = ns ? ns : 1;
     MCHECK(in.ensure(in_bytes));
-    MCHECK(tab.reserve(nblobs));
+    if (!ps) MCHECK(tab.reserve(nblobs));
     MCHECK(seg.ensure(8 * (nrecs ? nrecs : 1)));
     MCHECK(runs.ensure(16 * ns1));
     RestoreArgs a{};
     a.pool = d_pool;
     a.pool_bytes = pool_bytes;
-    a.blobs = reinterpret_cast<const PoolBlob*>(in.as<uint8_t>() + o_blobs);
+    a.blobs = ps ? ps->table : reinterpret_cast<const PoolBlob*>(in.as<uint8_t>() + o_blobs);
     a.nblobs = nblobs;
     a.rec = d_recs ? d_recs : reinterpret_cast<const ChunkRec*>(in.as<uint8_t>() + o_recs);
     a.nrec = nrecs;
@@ -107,8 +113,8 @@ struct RestoreWork {
     a.out_len = reinterpret_cast<const uint64_t*>(in.as<uint8_t>() + o_len);
     a.tpre = reinterpret_cast<const uint64_t*>(in.as<uint8_t>() + o_tpre);
     a.ns = ns;
-    a.tab = tab.p();
-    a.tab_mask = tab.mask();
+    a.tab = ps ? ps->index : tab.p();
+    a.tab_mask = ps ? ps->mask : tab.mask();
     a.seg = seg.as<uint64_t>();
     a.sfirst = runs.as<uint64_t>();
     a.slast = runs.as<uint64_t>() + ns1;
@@ -118,9 +124,10 @@ struct RestoreWork {
     int rc;
     mark(0);
     HCHECK(hipMemcpyAsync(in.p, hin, in_bytes, hipMemcpyHostToDevice, stream));
-    HCHECK(tab.clear(stream));
+    if (!ps) HCHECK(tab.clear(stream));
     HCHECK(hipMemsetAsync(runs.p, 0xFF, 16 * ns1, stream));
-    HCHECK(dbg("launch_restore_resolve", stream, launch_restore_resolve(a, stream, v.num_cus)));
+    HCHECK(dbg("launch_restore_resolve", stream,
+               launch_restore_resolve(a, !ps, stream, v.num_cus)));
     mark(1);
     if (verify && nblobs) {
       if ((rc = need_hasher(v.owner))) return rc;

@@ -33,47 +33,51 @@ struct WalkWork {
 
   // The host checks its own arrays (pointers, the blobs' bounds); every node is validated on the
   // device, level by level, with one small readback per level for the next frontier's size.
-  // Nothing of the result is allocated before every stream's verdict is in.
+  // Nothing of the result is allocated before every stream's verdict is in. With `ps` the table
+  // and the index are a bsg_pool's, read where they lie (bsg_pool_walk).
   int run(const RunView& v, const uint8_t* d_pool, uint64_t pool_bytes, const bsg_pool_blob* blobs,
           uint64_t nblobs, const uint8_t* roots, uint32_t nstreams, int flags, int32_t* status,
-          bsg_walk_info* info) {
+          bsg_walk_info* info, const PoolSrc* ps = nullptr) {
     const hipStream_t stream = v.stream;
     auto mark = [&](size_t i) { v.profile ? marks.record(i, stream) : void(); };
     valid = false;
     if (flags != 0 || nstreams > 65535) return BSG_EINVAL;
-    if ((!d_pool && pool_bytes) || (!blobs && nblobs) || (!roots && nstreams)) return BSG_EINVAL;
+    if ((!d_pool && pool_bytes) || (!blobs && !ps && nblobs) || (!roots && nstreams))
+      return BSG_EINVAL;
     const uintptr_t p0 = reinterpret_cast<uintptr_t>(d_pool);
     if (p0 + pool_bytes < p0) return BSG_EINVAL;
-    for (uint64_t k = 0; k < nblobs; ++k)
+    for (uint64_t k = 0; k < nblobs && !ps; ++k)
       if (blobs[k].off > pool_bytes || blobs[k].len > pool_bytes - blobs[k].off) return BSG_EINVAL;
+    if (ps && ps->used > pool_bytes) return BSG_EINVAL;
 
-    // the input block: header | sizes | status | blobs | Roots (the first three come back)
+    // the input block: header | sizes | status | blobs (the call's own table only) | Roots (the
+    // first three come back)
     auto pad16 = [](uint64_t x) { return (x + 15) & ~15ull; };
     const uint64_t o_sizes = sizeof(WalkHdr);
     const uint64_t o_status = o_sizes + pad16(8ull * nstreams);
     const uint64_t o_blobs = o_status + pad16(4ull * nstreams);
-    const uint64_t o_roots = o_blobs + pad16(sizeof(PoolBlob) * nblobs);
+    const uint64_t o_roots = o_blobs + (ps ? 0 : pad16(sizeof(PoolBlob) * nblobs));
     const uint64_t in_bytes = o_roots + pad16(32ull * nstreams);
     MCHECK(h_in.ensure(in_bytes));
     MCHECK(h_out.ensure(std::max<uint64_t>(o_blobs, 8ull * (nstreams + 1ull))));
     uint8_t* hin = h_in.as<uint8_t>();
     std::memset(hin, 0, o_blobs);
-    if (nblobs) std::memcpy(hin + o_blobs, blobs, sizeof(PoolBlob) * nblobs);
+    if (nblobs && !ps) std::memcpy(hin + o_blobs, blobs, sizeof(PoolBlob) * nblobs);
     if (nstreams) std::memcpy(hin + o_roots, roots, 32ull * nstreams);
 
     lv.resize(kWalkMaxDepth + 2);
     MCHECK(in.ensure(in_bytes));
-    MCHECK(tab.reserve(nblobs));
+    if (!ps) MCHECK(tab.reserve(nblobs));
     MCHECK(lv[0].items.ensure(sizeof(WalkItem) * nstreams));
     WalkArgs base{};
     base.pool = d_pool;
     base.pool_bytes = pool_bytes;
-    base.blobs = reinterpret_cast<const PoolBlob*>(in.as<uint8_t>() + o_blobs);
+    base.blobs = ps ? ps->table : reinterpret_cast<const PoolBlob*>(in.as<uint8_t>() + o_blobs);
     base.nblobs = nblobs;
     base.roots = in.as<uint8_t>() + o_roots;
     base.ns = nstreams;
-    base.tab = tab.p();
-    base.tab_mask = tab.mask();
+    base.tab = ps ? ps->index : tab.p();
+    base.tab_mask = ps ? ps->mask : tab.mask();
     base.hdr = in.as<WalkHdr>();
     base.sizes = reinterpret_cast<uint64_t*>(in.as<uint8_t>() + o_sizes);
     base.status = reinterpret_cast<uint32_t*>(in.as<uint8_t>() + o_status);
@@ -95,10 +99,12 @@ struct WalkWork {
     int rc;
     mark(0);
     HCHECK(hipMemcpyAsync(in.p, hin, in_bytes, hipMemcpyHostToDevice, stream));
-    HCHECK(tab.clear(stream));
-    HCHECK(dbg("launch_ref_index", stream,
-               launch_ref_index(base.blobs, nblobs, base.tab, base.tab_mask, &base.hdr->dd, stream,
-                                v.num_cus)));
+    if (!ps) {
+      HCHECK(tab.clear(stream));
+      HCHECK(dbg("launch_ref_index", stream,
+                 launch_ref_index(base.blobs, nblobs, base.tab, base.tab_mask, &base.hdr->dd,
+                                  stream, v.num_cus)));
+    }
     {
       WalkArgs a = base;
       a.items = lv[0].items.as<WalkItem>();

@@ -503,9 +503,10 @@ int bsg_engine_gc_compact(bsg_engine* eng, const uint8_t* d_pool, uint64_t pool_
  * The pool. One allocation of cap_bytes rounded up to 16, plus BSG_READ_SLACK, zero-filled at
  * creation, and a table of cap_blobs entries. Neither ever moves, so the device pointers below
  * stay valid for the pool's life and a walk, restore or gc may hold them. The capacity is fixed and
- * the pool only ever grows (no growth past the capacity, no delete; a pool is collected with
- * bsg_engine_gc_mark / bsg_engine_gc_compact into another buffer). bsg_pool_new returns NULL with
- * BSG_ENODEV (no such device) or BSG_ENOMEM in *err.
+ * the pool only ever grows (no growth past the capacity, no delete of single refs; a pool is
+ * collected into another, empty pool with bsg_pool_collect and emptied for reuse with
+ * bsg_pool_reset, below). bsg_pool_new returns NULL with BSG_ENODEV (no such device) or BSG_ENOMEM
+ * in *err.
  * Layout. Every blob starts at a multiple of 16 and the padding after it (at most 15 bytes) is
  * zero, so the pool (bsg_pool_bytes_device, with pool_bytes of bsg_pool_stat and the table of
  * bsg_pool_copy_table) is at all times a valid argument set for bsg_engine_walk,
@@ -571,6 +572,68 @@ int bsg_engine_pool_put(bsg_engine* eng, bsg_pool* pool, int flags, bsg_pool_put
  * device pointer below is NULL, which it also is after a put without items) or on a dead pool. */
 int bsg_pool_copy_where(bsg_pool* p, uint64_t* where, uint64_t cap);
 const uint64_t* bsg_pool_where_device(const bsg_pool* p);
+
+/* ---- a pool collected into a pool: gc.Run's Delete for data that lives in device memory ---- */
+/* Marks src from the Roots and appends its live blobs to dst, an empty pool; dst is then a pool
+ * like any other, and a put may append to it.
+ * The mark is bsg_engine_gc_mark's, rule for rule: liveness, the node rules, depth 64, the
+ * verdicts, status[] and every bsg_gc_info field. It runs over src's entries as they stand when
+ * the call has taken src's mutex, and reads src's table and src's own index where they lie on the
+ * device: no table crosses the host link and no index is built. It becomes the engine's current
+ * gc result: bsg_engine_gc_live_device and bsg_engine_copy_gc serve it (the table's entries are
+ * fetched from src's device table then), and bsg_engine_gc_compact takes src's
+ * bsg_pool_bytes_device / pool_bytes. That result reads src's table, so it holds only until src is
+ * reset or freed.
+ * The layout. Live blob k of src becomes dst's entry j = rank[k], the number of live blobs before
+ * it in index order, = {noff16[k], len, ref}; the bytes are what bsg_engine_gc_compact writes with
+ * BSG_GC_ALIGN16 (every blob at a multiple of 16, zero padding), and dst's `bytes` counter is the
+ * end of the last live blob's bytes. remap[k] = j for a live blob and UINT64_MAX for a dead one,
+ * for every k below src's nblobs at the call; dst owns remap until its next collect or reset.
+ * dst's table, bytes and remap are a function of src's contents and the Roots alone.
+ * All or nothing. Everything up to the readback of the totals writes the engine's gc buffers and
+ * nothing of dst. If need_blobs > cap_blobs or need_bytes > cap_bytes the call returns BSG_ENOMEM
+ * with info filled; after that or a failed mark dst is exactly as it was: bytes, table, index,
+ * counters, remap and where[]. A device error from then on marks dst dead: that call returns
+ * BSG_EDEVICE and later calls on dst BSG_ESTATE, as for a put. src is never written.
+ * Errors, in this order: BSG_EINVAL for a null engine or pool, src == dst, pools or engine on
+ * different devices, unknown flag bits, nroots > 2^32 - 1 or null roots with a count; BSG_ESTATE
+ * if either pool is dead, dst is not empty (nblobs != 0) or the engine has an enqueued,
+ * unfinished run; the mark's BSG_ENOTFOUND / BSG_ECORRUPT, with status and info->gc filled;
+ * BSG_ENOMEM; BSG_EDEVICE. Synchronous, on the engine's stream. Both pools' mutexes are held for
+ * the whole call and taken together, so A -> B beside B -> A on two threads cannot deadlock. */
+typedef struct bsg_pool_collect_info {
+  bsg_gc_info gc;                   /* exactly what bsg_engine_gc_mark fills */
+  uint64_t need_bytes, need_blobs;  /* what dst would hold; also filled on BSG_ENOMEM for want of capacity */
+} bsg_pool_collect_info;
+int bsg_pool_collect(bsg_engine* eng, bsg_pool* src, bsg_pool* dst,
+                     const uint8_t* roots, uint64_t nroots, /* host, nroots x 32 */
+                     int flags,                             /* BSG_GC_MISSING_LEAVES or 0 */
+                     int32_t* status /* host, nroots, or NULL */,
+                     bsg_pool_collect_info* info /* or NULL */);
+/* remap of the last successful collect into dst, up to cap entries to host memory. BSG_ESTATE
+ * before one (as the device pointer is NULL, which it also is after a collect of an empty src) or
+ * on a dead pool. */
+int bsg_pool_copy_remap(bsg_pool* dst, uint64_t* remap, uint64_t cap);
+const uint64_t* bsg_pool_remap_device(const bsg_pool* dst);
+/* Empties a pool for reuse, so two pools can alternate as source and destination: the counters go
+ * to zero, the index, the table and the used bytes are refilled as at creation, where[] and remap
+ * are dropped (their device pointers return NULL). A dead pool is usable again. Afterwards the
+ * pool is indistinguishable from a new one of the same capacity: the same puts give the same
+ * bytes. Synchronised before it returns. BSG_EINVAL for a null pool. */
+int bsg_pool_reset(bsg_pool* p);
+
+/* bsg_engine_walk and bsg_engine_restore_walk on a pool where it lies: the pool's device table and
+ * device index in the place of the host table and the per-call index, so nothing of the pool
+ * crosses the host link. Every rule, verdict, order of errors and output is theirs
+ * (bsg_engine_copy_walk and bsg_engine_walk_records_device serve the result as before); two codes
+ * come first: BSG_EINVAL for a null pool or one on another device than the engine, BSG_ESTATE for
+ * a dead pool. The pool's mutex is held for the call. bsg_pool_restore_walk refuses an output
+ * range that intersects the pool's allocation (BSG_EINVAL). */
+int bsg_pool_walk(bsg_engine* eng, bsg_pool* pool, const uint8_t* roots, uint32_t nstreams,
+                  int flags, int32_t* status, bsg_walk_info* info);
+int bsg_pool_restore_walk(bsg_engine* eng, bsg_pool* pool, uint8_t* d_out, uint64_t out_cap,
+                          const uint64_t* out_off, uint32_t nstreams, int flags,
+                          bsg_restore_info* info);
 
 /* Per-stage HIP event timing of later runs, and the last finished run's stage durations in
  * ms: [0] rolling scan (k_scan), [1] prefix/compact/select/chunks, [2] SHA-256 (k_sha, and the
