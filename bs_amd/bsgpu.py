@@ -168,6 +168,34 @@ class PoolCollectInfo(ctypes.Structure):
 
 
 assert ctypes.sizeof(PoolCollectInfo) == 88
+READ_VERIFY = 1        # BSG_READ_VERIFY (Engine.read, Pool.read)
+READ_RANGE_DTYPE = np.dtype([("root", "u1", (32,)), ("offset", "<u8"), ("len", "<u8")])
+assert READ_RANGE_DTYPE.itemsize == 48
+
+
+class ReadInfo(ctypes.Structure):
+    """bsg_read_info (include/bsgpu.h)."""
+    _fields_ = [("bad_range", ctypes.c_uint64), ("bad_blob", ctypes.c_uint64),
+                ("nnodes", ctypes.c_uint64), ("nleaves", ctypes.c_uint64),
+                ("bytes", ctypes.c_uint64), ("verified", ctypes.c_uint64),
+                ("depth", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+    def as_dict(self) -> dict:
+        return {k: int(getattr(self, k)) for k, _ in self._fields_ if k != "reserved"}
+
+
+assert ctypes.sizeof(ReadInfo) == 56
+
+
+def read_ranges(ranges) -> np.ndarray:
+    """A READ_RANGE_DTYPE array from one, or from (root, offset, len) triples."""
+    if isinstance(ranges, np.ndarray) and ranges.dtype == READ_RANGE_DTYPE:
+        return np.ascontiguousarray(ranges)
+    out = np.zeros(len(ranges), dtype=READ_RANGE_DTYPE)
+    for q, (root, offset, n) in enumerate(ranges):
+        out[q]["root"] = np.frombuffer(bytes(root), dtype=np.uint8)
+        out[q]["offset"], out[q]["len"] = offset, n
+    return out
 
 _lib = None
 
@@ -289,6 +317,13 @@ def lib() -> ctypes.CDLL:
         "bsg_pool_restore_walk": (ctypes.c_int, [vp, vp, vp, ctypes.c_uint64, u64p,
                                                  ctypes.c_uint32, ctypes.c_int,
                                                  ctypes.POINTER(RestoreInfo)]),
+        "bsg_engine_read": (ctypes.c_int, [vp, vp, ctypes.c_uint64, vp, ctypes.c_uint64, vp,
+                                           ctypes.c_uint32, vp, ctypes.c_uint64, vp, ctypes.c_int,
+                                           vp, vp, ctypes.POINTER(ReadInfo)]),
+        "bsg_pool_read": (ctypes.c_int, [vp, vp, vp, ctypes.c_uint32, vp, ctypes.c_uint64, vp,
+                                         ctypes.c_int, vp, vp, ctypes.POINTER(ReadInfo)]),
+        "bsg_pool_kill_debug": (ctypes.c_int, [vp]),
+        "bsg_engine_read_ms_debug": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_float)]),
         "bsg_pool_collect_ms_debug": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_float)]),
         "bsg_engine_pack_mode_debug": (ctypes.c_int, [vp, ctypes.c_int]),
         "bsg_engine_d2d_ms_debug": (ctypes.c_int, [vp, vp, vp, ctypes.c_uint64,
@@ -938,6 +973,36 @@ class Engine:
                                          RESTORE_VERIFY if verify else 0, ctypes.byref(info))
         return rc, info.as_dict()
 
+    def read(self, pool, blobs, ranges, out, out_off, flags: int = 0,
+             pool_bytes: int | None = None, out_cap: int | None = None):
+        """bsg_engine_read: the byte ranges `ranges` (READ_RANGE_DTYPE, or (root, offset, len)
+        triples) of the streams under their Roots, read out of the pool (POOL_BLOB_DTYPE table; a
+        DeviceBuffer, or a device address with pool_bytes) into out + out_off[q] (a DeviceBuffer,
+        or a device address with out_cap). Returns (rc, status, got, info): the return code, the
+        per-range status (int32) and byte counts (uint64) and the bsg_read_info as a dict; a
+        negative rc is returned, not raised."""
+        pp = pool.ptr if isinstance(pool, DeviceBuffer) else pool
+        op = out.ptr if isinstance(out, DeviceBuffer) else out
+        pool_bytes = pool.nbytes + READ_SLACK if pool_bytes is None else pool_bytes
+        out_cap = out.nbytes if out_cap is None else out_cap
+        blobs = np.ascontiguousarray(blobs, dtype=POOL_BLOB_DTYPE)
+        rg, oo = read_ranges(ranges), _u64(out_off)
+        assert len(rg) == len(oo)
+        status = np.zeros(max(len(rg), 1), dtype=np.int32)
+        got = np.zeros(max(len(rg), 1), dtype=np.uint64)
+        info = ReadInfo()
+        rc = lib().bsg_engine_read(self.h, pp, pool_bytes, blobs.ctypes.data, len(blobs),
+                                   rg.ctypes.data, len(rg), op, out_cap, oo.ctypes.data, flags,
+                                   status.ctypes.data, got.ctypes.data, ctypes.byref(info))
+        return rc, status[:len(rg)], got[:len(rg)], info.as_dict()
+
+    def read_ms(self) -> dict:
+        """The last read() / Pool.read() call's stages in ms (test tooling; needs profile() on)."""
+        out = (ctypes.c_float * 6)()
+        _check(lib().bsg_engine_read_ms_debug(self.h, out), "bsg_engine_read_ms_debug")
+        return dict(zip(("index", "levels", "placement", "resolve", "verify", "scatter"),
+                        (float(x) for x in out)))
+
     def dedup_ms(self) -> dict:
         """The last dedup() and pack_unique() calls in ms (test tooling; needs profile() on)."""
         out = (ctypes.c_float * 2)()
@@ -1095,7 +1160,7 @@ class Pool:
     """bsg_pool: a pool of blobs that lives in device memory across runs (Engine.pool_put fills
     it). Engine.walk, restore, restore_walk and gc_mark take it as
     `pool.ptr, pool.table(), ..., pool_bytes=pool.pool_bytes`; Engine.pool_walk,
-    pool_restore_walk and pool_collect take it where it lies."""
+    pool_restore_walk, pool_collect and Pool.read take it where it lies."""
 
     def __init__(self, cap_bytes: int, cap_blobs: int, device: int = 0):
         err = ctypes.c_int(0)
@@ -1140,6 +1205,22 @@ class Pool:
         if n:
             _check(lib().bsg_memcpy(self.device, out.ctypes.data, self.ptr, n, 1), "bsg_memcpy")
         return out[:n]
+
+    def read(self, eng: "Engine", ranges, out, out_off, flags: int = 0,
+             out_cap: int | None = None):
+        """bsg_pool_read: Engine.read() on this pool where it lies (its device table and index),
+        on `eng`. Returns (rc, status, got, info) as Engine.read()."""
+        op = out.ptr if isinstance(out, DeviceBuffer) else out
+        out_cap = out.nbytes if out_cap is None else out_cap
+        rg, oo = read_ranges(ranges), _u64(out_off)
+        assert len(rg) == len(oo)
+        status = np.zeros(max(len(rg), 1), dtype=np.int32)
+        got = np.zeros(max(len(rg), 1), dtype=np.uint64)
+        info = ReadInfo()
+        rc = lib().bsg_pool_read(eng.h if eng is not None else None, self.h, rg.ctypes.data,
+                                 len(rg), op, out_cap, oo.ctypes.data, flags, status.ctypes.data,
+                                 got.ctypes.data, ctypes.byref(info))
+        return rc, status[:len(rg)], got[:len(rg)], info.as_dict()
 
     def remap(self) -> np.ndarray:
         """bsg_pool_copy_remap: for every blob index of the source of the last successful collect

@@ -701,6 +701,63 @@ int bsg_pool_restore_walk(bsg_engine* e, bsg_pool* p, uint8_t* d_out, uint64_t o
                         out_cap, out_off, e->walk.sizes.data(), nstreams, flags, info, &ps);
 }
 
+// ---- byte ranges of streams read out of a pool ----------------------------------------------
+static_assert(sizeof(bsg_read_range) == 48 && sizeof(bsg_read_info) == 56, "bsg_read layouts");
+
+static void read_clear(uint32_t nranges, int32_t* status, uint64_t* got, bsg_read_info* info) {
+  if (info) *info = bsg_read_info{UINT64_MAX, UINT64_MAX, 0, 0, 0, 0, 0, 0};
+  if (nranges > 65535) return;  // (BSG_EINVAL: the arrays' lengths are not known to be that)
+  for (uint32_t q = 0; q < nranges; ++q) {
+    if (status) status[q] = BSG_OK;
+    if (got) got[q] = 0;
+  }
+}
+
+int bsg_engine_read(bsg_engine* e, const uint8_t* d_pool, uint64_t pool_bytes,
+                    const bsg_pool_blob* blobs, uint64_t nblobs, const bsg_read_range* ranges,
+                    uint32_t nranges, uint8_t* d_out, uint64_t out_cap, const uint64_t* out_off,
+                    int flags, int32_t* status, uint64_t* got, bsg_read_info* info) {
+  read_clear(nranges, status, got, info);
+  if (!e) return BSG_EINVAL;
+  int rc = e->setdev();
+  if (rc) return rc;
+  return e->read.run(e->view(), d_pool, pool_bytes, blobs, nblobs, ranges, nranges, d_out, out_cap,
+                     out_off, flags, status, got, info);
+}
+
+int bsg_pool_read(bsg_engine* e, bsg_pool* p, const bsg_read_range* ranges, uint32_t nranges,
+                  uint8_t* d_out, uint64_t out_cap, const uint64_t* out_off, int flags,
+                  int32_t* status, uint64_t* got, bsg_read_info* info) {
+  read_clear(nranges, status, got, info);
+  if (!e || !p || p->dev != e->dev) return BSG_EINVAL;
+  std::lock_guard<std::mutex> g(p->mu);
+  if (p->dead) return BSG_ESTATE;
+  int rc = e->setdev();
+  if (rc) return rc;
+  const PoolSrc ps = p->source();
+  return e->read.run(e->view(), p->bytes.as<const uint8_t>(), p->pool_bytes(), nullptr, p->nblobs,
+                     ranges, nranges, d_out, out_cap, out_off, flags, status, got, info, &ps);
+}
+
+// Test and measurement tooling (not in bsgpu.h): the last bsg_engine_read / bsg_pool_read call's
+// stages in ms (index + Roots, levels, placement, resolve + tiling, verify, scatter), with
+// bsg_engine_profile on.
+extern "C" int bsg_engine_read_ms_debug(const bsg_engine* e, float out[6]) {
+  if (!e || !out) return BSG_EINVAL;
+  if (!e->profile) return BSG_ESTATE;
+  for (int i = 0; i < 6; ++i) out[i] = e->read.ms[i];
+  return BSG_OK;
+}
+
+// Test tooling (not in bsgpu.h): the pool as a device error during an append leaves it, without
+// one: every later call on it is BSG_ESTATE until bsg_pool_reset.
+extern "C" int bsg_pool_kill_debug(bsg_pool* p) {
+  if (!p) return BSG_EINVAL;
+  std::lock_guard<std::mutex> g(p->mu);
+  p->dead = true;
+  return BSG_OK;
+}
+
 // Test and measurement tooling (not in bsgpu.h): the last successful bsg_pool_collect into p: its
 // k_pool_adopt in ms, timed with HIP events on the collecting engine's stream when its
 // bsg_engine_profile is on (else zero). The mark and the gather are bsg_engine_gc_ms_debug's.

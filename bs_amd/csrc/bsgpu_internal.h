@@ -277,6 +277,18 @@ struct WalkHdr {               // one call's verdicts and per-level totals, read
 };
 static_assert(sizeof(WalkHdr) % 16 == 0, "WalkHdr layout");
 
+// Byte ranges of streams read out of a pool (bsg_engine_read; bsgpu_read.inc): the walk with a
+// window per range, the restore's checks and scatter clipped to it.
+struct ReadHdr {               // one call's verdicts, read back by the host
+  WalkHdr w;                   // the pruned walk's header (w.dd.error: its bug guard)
+  RestoreHdr r;                // resolve, tiling and verify (r.dd.error: theirs); r.invalid bits
+                               //   1 | 2: a range's records do not cover its window (bug guard),
+                               //   4: a touched blob breaks the hash path's layout rules
+  uint64_t verified;           // the touched blobs' lens, summed
+  uint64_t pad_;
+};
+static_assert(sizeof(ReadHdr) % 16 == 0 && offsetof(ReadHdr, r) % 16 == 0, "ReadHdr layout");
+
 // A pool garbage-collected on the device from its Roots (bsg_engine_gc_mark / _compact;
 // bsgpu_gc.inc). The mark is the walk's breadth-first search without covers and with every blob
 // expanded once: level L's frontier holds the node blobs whose nearest Root is L edges away.

@@ -2617,5 +2617,6 @@ hipError_t launch_sha_blobs(const BlobShaArgs& a, hipStream_t s, int num_cus) {
 #include "bsgpu_walk.inc"
 #include "bsgpu_gc.inc"
 #include "bsgpu_pool.inc"
+#include "bsgpu_read.inc"
 
 }  // namespace bsg

@@ -292,6 +292,10 @@ struct RestoreArgs {
   uint64_t* slast;           // [ns] and its last
   uint8_t* out;
   RestoreHdr* hdr;
+  // bsg_engine_read (null: none): stream s's output is bytes [win0[s], win0[s] + out_len[s]) of
+  // the stream, and its records are the chunks under them, with their own offsets and whole lens
+  const uint64_t* win0;      // [ns]
+  uint8_t* touched;          // [nblobs] set for every blob a record resolves to
 };
 // the index of the pool's refs (index: built here into a.tab; else a.tab holds it already), every
 // record resolved against it, the records' tiling checked
@@ -339,6 +343,12 @@ struct WalkArgs {
   uint64_t* part;            // [sum_parts(n)] workgroup sums of a prefix pass
   ChunkRec* rec;             // [nrec] the result
   uint64_t nrec;
+  // bsg_engine_read (null: none): per-stream windows, and what the pruned walk keeps of them
+  const uint64_t* win;       // [2 * ns] stream s follows a child iff its cover has a byte in
+                             //   [win[2s], win[2s + 1])
+  uint8_t* touched;          // [nblobs] set for every Root and followed `nodes` child found
+  uint64_t* lfirst;          // [n] a leaf node's first followed child
+  uint64_t* lpre;            // [n + 1] exclusive prefix of the leaf nodes' followed children
 };
 hipError_t launch_walk_roots(const WalkArgs& a, hipStream_t s, int num_cus);
 // validate and count the level's nodes, then call and cnode
@@ -437,5 +447,34 @@ struct AdoptArgs {
   DedupHdr* hdr;
 };
 hipError_t launch_pool_adopt(const AdoptArgs& a, hipStream_t s, int num_cus);
+
+// bsg_engine_read (bsgpu_read.inc): byte ranges of streams out of a pool. The walk is
+// bsg_engine_walk's with WalkArgs::win set (launch_walk_roots / _count / _emit), the scatter
+// bsg_engine_restore's with RestoreArgs::win0 set (launch_restore_scatter); what lies between is here.
+// placement, bottom-up: a leaf node's run of followed children and the records below every node
+hipError_t launch_read_nrec(const WalkArgs& a, hipStream_t s, int num_cus);
+// top-down: every node's first record, then the followed leaf children's records (leaf_bound:
+// the level's `leaves` children, at least as many)
+hipError_t launch_read_place(const WalkArgs& a, uint64_t leaf_bound, hipStream_t s, int num_cus);
+// every record resolved and its blob touched; each stream's run held to cover its window
+hipError_t launch_read_resolve(const RestoreArgs& a, hipStream_t s, int num_cus);
+// The touched blobs (BSG_READ_VERIFY). tpre [nblobs + 1]: the exclusive prefix of touched; tlist
+// [tpre[nblobs]]: their indices, ascending; each is held to the hash path's layout rules
+// (RestoreHdr::invalid) and its len added to *verified.
+struct TouchArgs {
+  RestoreArgs r;
+  uint64_t* tpre;
+  uint64_t* tlist;
+  uint64_t ntouched;         // tpre[nblobs], read back (the hash batches)
+  uint64_t* verified;
+  uint64_t* part;            // [sum_parts(nblobs)]
+};
+hipError_t launch_read_touched(const TouchArgs& a, hipStream_t s, int num_cus);
+// touched blobs tlist[t0 .. t0 + n) as the descriptors of a hash run, and that run's records
+// against their refs (RestoreHdr::bad_blob: the smallest blob index that fails)
+hipError_t launch_read_descs(const TouchArgs& a, uint64_t t0, uint32_t n, StreamDesc* d,
+                             hipStream_t s, int num_cus);
+hipError_t launch_read_compare(const TouchArgs& a, uint64_t t0, uint32_t n, const ChunkRec* hashed,
+                               const Counters* hctr, hipStream_t s, int num_cus);
 
 }  // namespace bsg

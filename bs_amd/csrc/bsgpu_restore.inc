@@ -88,23 +88,27 @@ __global__ __launch_bounds__(256) void k_rs_streams(RestoreArgs a) {
 }
 
 // ---- verify: the pool's blobs as the descriptors of a hash run, its records against the refs ---
+// blob k as a hash run's descriptor (empty, and the error flag, if it breaks the hash path's rules)
+__device__ __forceinline__ StreamDesc rs_blob_desc(const RestoreArgs& a, uint64_t k) {
+  uint64_t off = a.blobs[k].off, len = a.blobs[k].len;
+  if ((off & 15) || off > a.pool_bytes || len > a.pool_bytes - off || len >= (1ull << 40)) {
+    rs_error(a.hdr, 8);
+    off = 0;
+    len = 0;
+  }
+  StreamDesc sd = {};
+  sd.data_off = off;
+  sd.len = len;
+  sd.finalize = 1;
+  sd.mid[0] = 0x6a09e667; sd.mid[1] = 0xbb67ae85; sd.mid[2] = 0x3c6ef372; sd.mid[3] = 0xa54ff53a;
+  sd.mid[4] = 0x510e527f; sd.mid[5] = 0x9b05688c; sd.mid[6] = 0x1f83d9ab; sd.mid[7] = 0x5be0cd19;
+  return sd;
+}
+
 __global__ __launch_bounds__(256) void k_rs_descs(RestoreArgs a, uint64_t b0, uint32_t n,
                                                   StreamDesc* d) {
-  for (uint32_t b = blockIdx.x * blockDim.x + threadIdx.x; b < n; b += gridDim.x * blockDim.x) {
-    uint64_t off = a.blobs[b0 + b].off, len = a.blobs[b0 + b].len;
-    if ((off & 15) || off > a.pool_bytes || len > a.pool_bytes - off || len >= (1ull << 40)) {
-      rs_error(a.hdr, 8);
-      off = 0;
-      len = 0;
-    }
-    StreamDesc sd = {};
-    sd.data_off = off;
-    sd.len = len;
-    sd.finalize = 1;
-    sd.mid[0] = 0x6a09e667; sd.mid[1] = 0xbb67ae85; sd.mid[2] = 0x3c6ef372; sd.mid[3] = 0xa54ff53a;
-    sd.mid[4] = 0x510e527f; sd.mid[5] = 0x9b05688c; sd.mid[6] = 0x1f83d9ab; sd.mid[7] = 0x5be0cd19;
-    d[b] = sd;
-  }
+  for (uint32_t b = blockIdx.x * blockDim.x + threadIdx.x; b < n; b += gridDim.x * blockDim.x)
+    d[b] = rs_blob_desc(a, b0 + b);
 }
 
 __global__ __launch_bounds__(256) void k_rs_compare(RestoreArgs a, uint64_t b0, uint32_t n,
@@ -130,20 +134,35 @@ struct RsOffset {  // seg_find's key: a record's offset in its stream
   __device__ uint64_t operator()(uint64_t k) const { return rec[k].offset; }
 };
 
-// the segment of stream s (slen bytes) that holds byte `pos`, among records [*k, k1]
+// the segment of stream s (slen bytes) that holds byte `pos`, among records [*k, k1]. With a
+// window (a.win0) pos and the segment are output positions: output byte p is stream byte w0 + p,
+// a record that starts before the window gives its bytes from w0 on, one that ends after it its
+// bytes up to the window's end, and no byte outside a blob is read.
 __device__ __forceinline__ bool rs_locate(const RestoreArgs& a, uint32_t s, uint64_t slen,
                                           uint64_t* k, uint64_t k1, uint64_t pos, GatherSeg* g) {
-  *k = seg_find(*k, k1 + 1, pos, RsOffset{a.rec});
+  const uint64_t w0 = a.win0 ? a.win0[s] : 0;
+  const uint64_t sp = w0 + pos;  // (the tiling check: the window lies inside the records)
+  *k = seg_find(*k, k1 + 1, sp, RsOffset{a.rec});
   const uint64_t off = a.rec[*k].offset, len = a.rec[*k].len, so = a.seg[*k];
   g->src = nullptr;
-  if (a.rec[*k].stream != s || pos < off || off > slen || len > slen - off || pos - off >= len ||
-      so > a.pool_bytes || len > a.pool_bytes - so) {
+  bool bad = a.rec[*k].stream != s || sp < pos || sp < off || sp - off >= len ||
+             so > a.pool_bytes || len > a.pool_bytes - so;
+  if (!a.win0) bad = bad || off > slen || len > slen - off;
+  else bad = bad || off + len < off || pos >= slen;
+  if (bad) {
     rs_error(a.hdr, 256);
     return false;
   }
-  g->src = a.pool + so;
-  g->b0 = off;
-  g->b1 = off + len;
+  if (!a.win0) {
+    g->src = a.pool + so;
+    g->b0 = off;
+    g->b1 = off + len;
+    return true;
+  }
+  const uint64_t skip = off < w0 ? w0 - off : 0;  // the record's bytes before the window
+  g->src = a.pool + so + skip;
+  g->b0 = off + skip - w0;
+  g->b1 = min(off + len - w0, slen);
   return true;
 }
 
@@ -154,8 +173,9 @@ __global__ __launch_bounds__(256) void k_rs_scatter(RestoreArgs a) {
     const uint64_t s = seg_find(0, a.ns, b, [&a](uint64_t k) { return a.tpre[k]; });
     const uint64_t slen = a.out_len[s], r0 = a.sfirst[s], r1 = a.slast[s];
     const uint64_t t0 = a.tpre[s] <= b ? (b - a.tpre[s]) * kRestoreTile : ~0ull;
+    const uint64_t w0 = a.win0 ? a.win0[s] : 0;  // (bsg_engine_read: the tile's stream bytes)
     sh[0] = 0;
-    if (t0 >= slen || r0 > r1 || r1 >= a.nrec) {
+    if (t0 >= slen || r0 > r1 || r1 >= a.nrec || w0 + slen < w0) {
       rs_error(a.hdr, 128);
     } else {
       const uint64_t t1 = min(t0 + (uint64_t)kRestoreTile, slen);
@@ -163,8 +183,8 @@ __global__ __launch_bounds__(256) void k_rs_scatter(RestoreArgs a) {
       sh[1] = s;
       sh[2] = t0;
       sh[3] = t1;
-      sh[4] = seg_find(r0, r1 + 1, t0, RsOffset{a.rec});
-      sh[5] = seg_find(sh[4], r1 + 1, t1 - 1, RsOffset{a.rec});
+      sh[4] = seg_find(r0, r1 + 1, w0 + t0, RsOffset{a.rec});
+      sh[5] = seg_find(sh[4], r1 + 1, w0 + t1 - 1, RsOffset{a.rec});
     }
   }
   __syncthreads();

@@ -62,6 +62,7 @@ __global__ __launch_bounds__(256) void k_wk_roots(WalkArgs a) {
     if (r[0] | r[1] | r[2] | r[3]) {  // (bs.Zero: an empty stream)
       w.blob = wk_probe(a, r);
       if (w.blob == kWalkDead) wk_status(a, s, kWalkNotFound);
+      else if (a.touched) a.touched[w.blob] = 1;  // (bsg_engine_read)
     }
     a.items[s] = w;
   }
@@ -274,9 +275,21 @@ __device__ __forceinline__ bool wk_child(const WalkArgs& a, uint64_t i, uint64_t
   return true;
 }
 
+// ---- stream s's window (bsg_engine_read; a.win null: none, every child is followed) -------------
+// true if the cover [off, end) has a byte in [win[2s], win[2s + 1])
+__device__ __forceinline__ bool wk_in_window(const WalkArgs& a, uint32_t s, uint64_t off,
+                                             uint64_t end) {
+  if (!a.win) return true;
+  if (s >= a.ns) return false;
+  const uint64_t w0 = a.win[2ull * s], w1 = a.win[2ull * s + 1];
+  return w0 < w1 && off < w1 && w0 < end;
+}
+
 // ---- emit: one thread per child ------------------------------------------------------------------
 // A `nodes` child becomes the next frontier's entry cnode[i] + k (dead if the pool lacks it), so a
-// frontier stays sorted by (stream, offset); a `leaves` child is held to its cover.
+// frontier stays sorted by (stream, offset); a `leaves` child is held to its cover. With windows a
+// child whose cover misses its stream's window is not probed: a `nodes` child leaves a dead entry
+// without a verdict, a `leaves` child nothing; an empty cover is the listing node's fault.
 __global__ __launch_bounds__(256) void k_wk_emit(WalkArgs a) {
   const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
   for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < a.nchild; t += stride) {
@@ -289,6 +302,15 @@ __global__ __launch_bounds__(256) void k_wk_emit(WalkArgs a) {
       continue;
     }
     const bool covered = c.off < c.end;
+    if (a.win && !(covered && wk_in_window(a, s, c.off, c.end))) {
+      if (!covered) wk_status(a, s, kWalkCorrupt);
+      if (a.nodes[i].kind == 1 && !a.last) {
+        const uint64_t slot = a.cnode[i] + k;
+        if (slot >= a.nnext) wk_error(a, 128);
+        else a.next[slot] = WalkItem{kWalkDead, c.off, 0, i, s, 0};
+      }
+      continue;
+    }
     if (a.nodes[i].kind == 1) {
       if (a.last) {  // its children would lie deeper than kWalkMaxDepth
         wk_status(a, s, kWalkCorrupt);
@@ -304,6 +326,7 @@ __global__ __launch_bounds__(256) void k_wk_emit(WalkArgs a) {
       if (f == kDedupEmpty) wk_status(a, s, kWalkNotFound);
       else if (!covered) wk_status(a, s, kWalkCorrupt);
       else w.blob = f;
+      if (a.touched && w.blob != kWalkDead) a.touched[f] = 1;
       a.next[slot] = w;
     } else {
       const uint64_t f = wk_probe(a, c.ref);

@@ -53,7 +53,7 @@ uint64_t data_span(const std::vector<StreamDesc>& descs) {
   return hi;
 }
 
-// What a pass over a finished run (trees, dedup and pack, restore, walk, gc) takes from its engine: where
+// What a pass over a finished run (trees, dedup and pack, restore, walk, gc, read) takes from its engine: where
 // it works, the run's inputs and results; `owner` only to hand on to need_hasher / hash_batches.
 struct RunView {
   bsg_engine* owner;
@@ -87,6 +87,7 @@ int hash_batches(bsg_engine* owner, DevBuf& dbuf, uint64_t n, const uint8_t* dat
 #include "host_restore.h"
 #include "host_walk.h"
 #include "host_gc.h"
+#include "host_read.h"
 #include "host_blobpool.h"
 
 struct bsg_engine {
@@ -140,6 +141,7 @@ struct bsg_engine {
   RestoreWork restore;
   WalkWork walk;
   GcWork gc;
+  ReadWork read;
   RunView view() {
     return RunView{this, stream, num_cus, profile, run_done, run_done && !snapshot && !hash_mode,
                    enqueued, d_data, &descs, streams.as<StreamDesc>(), nstreams,

@@ -635,6 +635,94 @@ int bsg_pool_restore_walk(bsg_engine* eng, bsg_pool* pool, uint8_t* d_out, uint6
                           const uint64_t* out_off, uint32_t nstreams, int flags,
                           bsg_restore_info* info);
 
+/* ---- byte ranges of streams read out of a pool: split.Reader's Seek + Read for many ranges ---- */
+/* split.Reader's Seek followed by Read (split/split.go:194-298) descends from the Root by the
+ * children's offsets, fetches only the nodes on the way and the chunks under the requested bytes,
+ * and discards the part of the first chunk before the position. bsg_engine_read does that for
+ * many ranges at once: the work and the workspace grow with the bytes asked for, not with the
+ * streams' sizes, and blobs far from a range need not be in the pool. The pool means what it
+ * means for bsg_engine_walk: blobs may start at any byte, of two blobs under one ref the one with
+ * the smaller index is used, refs are trusted labels. The same Root may appear in many ranges.
+ * What a range means. Range q is bytes [offset, offset + len) of the stream under ranges[q].root,
+ * offset + len saturating at 2^64 - 1. With size the Root node's size (0 for 32 zero bytes, an
+ * empty stream), got[q] = min(len, size - min(offset, size)): an offset at or past the end gives
+ * got[q] == 0 and status BSG_OK, the Reader's EOF with n == 0. On success
+ * d_out[out_off[q] .. + got[q]) holds bytes [offset, offset + got[q]) of the stream and no other
+ * byte of d_out is written: the rest of a range's len bytes, the gaps between ranges and the tail
+ * of a range's last 16-byte vector stay as they were.
+ * What is visited. The Root blob of every non-zero Root is visited, whatever the range, and held
+ * to the walk's node rules (a Root's offset is 0). Child i of a visited node covers the bytes from
+ * its offset to the next child's offset (the last one to the node's offset + size), as in the
+ * walk; it is followed if and only if its cover has a byte in [offset, offset + len). A followed
+ * `nodes` child is probed, read, held to its cover and validated, and a followed `leaves` child
+ * probed and its table len held to its cover, exactly as in bsg_engine_walk; `nodes` children at
+ * depth 64 are refused unread. A child that is not followed is neither probed nor read: the pool
+ * need not hold it and its bytes are never examined, but the node that lists it must still parse
+ * as a whole, and a visited node whose last child starts at or past the node's end (an empty
+ * cover) is corrupt whatever the range. status[q], info and the output are therefore a function
+ * of the arguments alone. status[q] is BSG_ENOTFOUND if the Root or a followed child is not in
+ * the pool, else BSG_ECORRUPT if a visited node or a followed child's cover breaks a rule, else
+ * BSG_OK.
+ * BSG_READ_VERIFY. The structural walk runs first, on trusted labels; it is bounded and
+ * range-checked whatever the bytes are. Then every distinct touched blob (the visited nodes and
+ * the followed leaves) is hashed once on the engine's hash runs and held to its ref, before a
+ * byte of d_out is written. Untouched blobs are not hashed, so `verified` is a fraction of the
+ * pool. The hash path's layout rules (bsg_engine_hash) apply to the touched blobs only: d_pool
+ * and their offsets multiples of 16, lens under 2^40, BSG_READ_SLACK readable bytes of pool_bytes
+ * after each of them.
+ * All or nothing. Every verdict, verification included, is in before the scatter is launched: on
+ * any failure d_out is untouched and got[] is zero.
+ * Returns, in this order: BSG_EINVAL, before anything is enqueued, for a null pointer with a
+ * non-zero count, nranges > 65,535, unknown flag bits, d_out or an out_off[q] not a multiple of
+ * 16, an out_off[q] beyond out_cap, an out_off[q] + len that exceeds out_cap when len is below
+ * 2^63 (a larger len is held to the stream's size), or a blob that ends past pool_bytes;
+ * BSG_EINVAL, once the sizes are back, for an out_off[q] + got[q] beyond out_cap, two ranges'
+ * [out_off, out_off + got) that intersect or one that intersects the pool (got taken from the
+ * Root node's size whatever the range's status); BSG_ENOTFOUND if any range's status is that;
+ * BSG_ECORRUPT if any range's status is that; with the flag, BSG_EINVAL if a touched blob breaks
+ * a layout rule above, then BSG_ECORRUPT if a touched blob's SHA-256 is not its ref (bad_blob);
+ * BSG_ESTATE if the engine has an enqueued, unfinished run; BSG_ENOMEM; BSG_EDEVICE for a device
+ * sanity word. status and info's bad_range, nnodes and depth are filled whenever both groups of
+ * layout rules held, nleaves when every status is BSG_OK, bad_blob and verified when the hash
+ * runs have finished. Synchronous, on the engine's stream. The read owns its workspace and publishes
+ * nothing: the engine's last run, dedup result, tree, walk, restore and gc results stay valid,
+ * and an engine needs no run before it reads. */
+typedef struct bsg_read_range {
+  uint8_t  root[32];   /* the stream's Root; 32 zero bytes: an empty stream */
+  uint64_t offset;     /* Seek(offset, io.SeekStart) */
+  uint64_t len;        /* len(buf) */
+} bsg_read_range;      /* 48 bytes */
+#define BSG_READ_VERIFY 1 /* hash every blob the read touches, and only those */
+typedef struct bsg_read_info {
+  uint64_t bad_range;  /* smallest range index whose status is not BSG_OK, else UINT64_MAX */
+  uint64_t bad_blob;   /* with the flag: smallest touched pool blob whose bytes do not hash to its
+                        * ref, else UINT64_MAX */
+  uint64_t nnodes;     /* node blobs visited, over all ranges (a node shared by two ranges counts
+                        * twice, as in the walk) */
+  uint64_t nleaves;    /* leaf children followed, over all ranges */
+  uint64_t bytes;      /* sum of got[] (0 on any failure) */
+  uint64_t verified;   /* with the flag: sum of len over the distinct touched blobs */
+  uint32_t depth, reserved;
+} bsg_read_info;
+int bsg_engine_read(bsg_engine* eng,
+                    const uint8_t* d_pool, uint64_t pool_bytes,            /* device */
+                    const bsg_pool_blob* blobs, uint64_t nblobs,           /* host */
+                    const bsg_read_range* ranges, uint32_t nranges,        /* host */
+                    uint8_t* d_out, uint64_t out_cap,                      /* device */
+                    const uint64_t* out_off,                               /* host, nranges */
+                    int flags,
+                    int32_t* status, uint64_t* got,                        /* host, nranges, or NULL */
+                    bsg_read_info* info);                                  /* or NULL */
+/* bsg_engine_read on a pool where it lies, as bsg_pool_walk is bsg_engine_walk: the pool's device
+ * table and device index in the place of the host table and the per-call index. Every rule,
+ * verdict, order of errors and output is bsg_engine_read's; two codes come first: BSG_EINVAL for a
+ * null pool or one on another device than the engine, BSG_ESTATE for a dead pool. The pool's mutex
+ * is held for the call, and an output that intersects the pool's allocation is refused
+ * (BSG_EINVAL). */
+int bsg_pool_read(bsg_engine* eng, bsg_pool* pool, const bsg_read_range* ranges, uint32_t nranges,
+                  uint8_t* d_out, uint64_t out_cap, const uint64_t* out_off, int flags,
+                  int32_t* status, uint64_t* got, bsg_read_info* info);
+
 /* Per-stage HIP event timing of later runs, and the last finished run's stage durations in
  * ms: [0] rolling scan (k_scan), [1] prefix/compact/select/chunks, [2] SHA-256 (k_sha, and the
  * early chains' tail). Timed on the engine's own stream. enable: 0 off, 1 every stage (four
