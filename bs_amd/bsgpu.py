@@ -334,6 +334,10 @@ def lib() -> ctypes.CDLL:
         "bsg_engine_timeline": (ctypes.c_int, [vp, u64p]),
         "bsg_engine_tiers_debug": (ctypes.c_int, [vp, u64p]),
         "bsg_engine_early_min_debug": (ctypes.c_int, [vp, ctypes.c_uint64]),
+        "bsg_engine_host_tail": (ctypes.c_int, [vp, u64p]),
+        "bsg_engine_host_tail_debug": (ctypes.c_int, [vp, ctypes.c_uint64, ctypes.c_uint32,
+                                                      ctypes.c_int, ctypes.c_uint64]),
+        "bsg_host_sha256_debug": (ctypes.c_int, [vp, ctypes.c_uint64, ctypes.c_int, vp]),
         "bsg_engine_early_picks_debug": (ctypes.c_int, [vp, u64p]),
         "bsg_engine_rescan_debug": (ctypes.c_uint64, [vp]),
         "bsg_engine_regions_debug": (ctypes.c_int, [vp, vp, ctypes.c_uint64]),
@@ -424,7 +428,7 @@ def _p(a: np.ndarray, ct):
 
 # bsg_debug_set
 (KNOB_SEQ_WAIT, KNOB_LONG_MODE, KNOB_VERIFY_WINDOW, KNOB_EARLY, KNOB_POLL, KNOB_COPY_NT,
- KNOB_LIGHT_BYTES) = range(1, 8)
+ KNOB_LIGHT_BYTES, KNOB_HOST_TAIL) = range(1, 9)
 
 
 def debug_get(knob: int) -> int:
@@ -1042,7 +1046,25 @@ class Engine:
                 out[tag] = {"blocks": nb, "cycles_per_block": round(cyc / nb, 1),
                             "clock_ghz": round(cyc / (rt * 10.0), 3),
                             "us_per_block": round(rt * 0.01 / nb, 4)}
+        t = np.zeros(12, dtype=np.uint64)
+        _check(lib().bsg_engine_host_tail(self.h, _p(t, ctypes.c_uint64)), "bsg_engine_host_tail")
+        out["host_tail"] = {"chunks": int(t[0]), "bytes": int(t[1]), "cut_blocks": int(t[2]),
+                            "gather_us": int(t[3]), "host_done_us": int(t[4]),
+                            "impl": "x86-sha" if int(t[5]) == 1 else "portable",
+                            "threads": int(t[6]), "host_rate_bytes_s": int(t[7]),
+                            "longest_blocks": int(t[8]), "longest_left_blocks": int(t[9]),
+                            "host_blocks": int(t[10]), "cpuid_sha": bool(t[11])}
         return out
+
+    def set_host_tail(self, min_bytes: int = 512 << 20, force_cut: int = 0,
+                      portable: bool = False, ring_bytes: int = 0) -> None:
+        """bsg_engine_host_tail_debug (test tooling, not in bsgpu.h): this engine's later runs may
+        hand chunks to the host from `min_bytes` on; `force_cut` > 0 takes every chunk of at least
+        that many SHA-256 blocks (as far as the ring holds them) instead of the cost model's
+        choice; `portable` forces the portable hash; `ring_bytes` > 0 sets the ring's size."""
+        _check(lib().bsg_engine_host_tail_debug(self.h, int(min_bytes), int(force_cut),
+                                                int(bool(portable)), int(ring_bytes)),
+               "bsg_engine_host_tail_debug")
 
     def tiers(self) -> dict:
         """bsg_engine_tiers_debug (test tooling, not in bsgpu.h): how k_bucket_scan split the last

@@ -9,7 +9,8 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libbsgpu.so")
-SOURCES = ["bsgpu_kernels.hip", "bsgpu_host.cpp", "bs_split.cpp", "bs_filestore.cpp"]
+SOURCES = ["bsgpu_kernels.hip", "bsgpu_host.cpp", "host_sha256.cpp", "bs_split.cpp",
+           "bs_filestore.cpp"]
 ARCH = os.environ.get("BSG_OFFLOAD_ARCH", "gfx950")
 _INCLUDE = re.compile(r'^[ \t]*#[ \t]*include[ \t]*"([^"]+)"', re.M)
 

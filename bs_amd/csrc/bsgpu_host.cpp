@@ -40,6 +40,7 @@
 #include "bsgpu_launch.h"
 #include "buzhash32_table.inc"
 #include "host_pool.h"
+#include "host_sha256.h"
 
 using namespace bsg;
 
@@ -70,7 +71,8 @@ int64_t bsg_debug_get(int k) {
 int bsg_debug_set(int k, int64_t value) {
   if (k < BSG_KNOB_SEQ_WAIT || k > BSG_KNOB_LAST || value < 0) return BSG_EINVAL;
   if (k == BSG_KNOB_LONG_MODE && value > 2) return BSG_EINVAL;
-  if ((k == BSG_KNOB_EARLY || k == BSG_KNOB_POLL || k == BSG_KNOB_COPY_NT) && value > 1)
+  if ((k == BSG_KNOB_EARLY || k == BSG_KNOB_POLL || k == BSG_KNOB_COPY_NT ||
+       k == BSG_KNOB_HOST_TAIL) && value > 1)
     return BSG_EINVAL;
   if (k == BSG_KNOB_SEQ_WAIT && value > (int64_t)UINT32_MAX) return BSG_EINVAL;  // a u32 poll count
   knob(k).store(value);
@@ -148,6 +150,7 @@ int bsg_init(int device) {
   uint64_t n = 0;
   if (!buf) rc = BSG_ENOMEM;
   eng->early_min = 0;  // the early-chain kernels too (they pick nothing in 64 KiB)
+  (void)bsg_engine::host_sha_rate(false);  // the host tail's cost model: one worker's SHA-256 rate
   if (rc == BSG_OK) rc = bsg_fill_splitmix(device, buf, kWarm, 1, eng->stream);
   if (rc == BSG_OK) rc = bsg_engine_run(eng, buf, &off, &len, 1, nullptr);
   if (rc == BSG_OK) rc = bsg_engine_finish(eng, &n);
@@ -230,6 +233,8 @@ void bsg_engine_destroy(bsg_engine* e) {
   // a failed run may have left early chains (k_pick / k_early on estream) that the engine
   // stream never waited for: they read cand, ctr and the data, so they end before any release
   if (e->estream) hipStreamSynchronize(e->estream);
+  // the hash workers leave an unfinished tail and are joined before its pinned buffers go
+  e->workers.reset();
   const int dev = e->dev;
   const hipStream_t estream = e->estream, stream = e->borrowed_stream ? nullptr : e->stream;
   delete e;  // every buffer and event of the run and of the passes, now that nothing runs
@@ -946,6 +951,38 @@ int bsg_engine_diag(const bsg_engine* e, uint64_t out[16]) {
   out[13] = e->last.nshort;
   out[14] = e->last.ntickets;
   out[15] = e->last.total_blocks;
+  return BSG_OK;
+}
+
+int bsg_engine_host_tail(const bsg_engine* e, uint64_t out[12]) {
+  if (!e || !out) return BSG_EINVAL;
+  const bsg_engine::TailStat& t = e->tail_stat;
+  out[0] = t.chunks;
+  out[1] = t.bytes;
+  out[2] = t.cut;
+  out[3] = (uint64_t)(t.gather_ms > 0 ? t.gather_ms * 1000.f : 0.f);
+  out[4] = (uint64_t)std::max<int64_t>(0, t.host_done_us);
+  out[5] = (uint64_t)t.impl;
+  out[6] = (uint64_t)t.threads;
+  out[7] = (uint64_t)t.host_rate;
+  out[8] = t.longest_all;
+  out[9] = t.longest_left;
+  out[10] = t.blocks;
+  out[11] = sha256_have_x86() ? 1 : 0;
+  return BSG_OK;
+}
+
+// Test tooling (not in include/bsgpu.h), beside bsg_engine_early_min_debug: the run size from
+// which this engine's later runs may hand chunks to the host (512 MiB by default), a forced cut
+// in SHA-256 blocks (every chunk of at least that many, as far as the ring holds them; 0: the
+// cost model), the portable hash in the workers, and the ring's size in bytes (0: by the run's).
+extern "C" int bsg_engine_host_tail_debug(bsg_engine* e, uint64_t min_bytes, uint32_t force_cut,
+                                          int portable, uint64_t ring_bytes) {
+  if (!e || e->enqueued || (ring_bytes && ring_bytes < 4096)) return BSG_EINVAL;
+  e->tail_min = min_bytes;
+  e->tail_force_cut = force_cut;
+  e->tail_portable = portable != 0;
+  e->tail_ring_force = ring_bytes;
   return BSG_OK;
 }
 

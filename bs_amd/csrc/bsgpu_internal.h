@@ -166,6 +166,46 @@ struct Early {
 };
 static_assert(sizeof(Early) % 16 == 0, "Early layout");
 
+// Host tail (bsg_engine, "Host tail"; bsgpu_tail.inc). A lightly loaded run's step is its longest
+// chunk's serial chain, so the run's longest chunks leave k_sha's queues the way the early picks
+// do (jinfo = kNoJob): their bytes go through a pinned ring to host threads (host_sha256.h), which
+// hash them while k_sha hashes the rest, and k_offload_fix writes their records.
+constexpr uint32_t kTailBuckets = 256;       // job lengths by bucket of (longest / 256 + 1) blocks
+constexpr uint32_t kTailMaxItems = 4096;     // chunks one run hands to the host at most
+constexpr uint32_t kTailMinBlocks = 256;     // the cost model never offloads below 16 KiB
+constexpr uint32_t kTailSlotAlign = 256;     // a chunk's place in the ring
+struct TailItem {              // == HashItem (host_sha256.h)
+  uint64_t job;                // the chunk's record index
+  uint64_t start;              // its stream offset
+  uint64_t len;
+  uint64_t off;                // of its first byte in the ring (off % 16 == source address % 16)
+  uint32_t stream;
+  uint32_t level;
+};
+static_assert(sizeof(TailItem) == 40, "TailItem layout");
+struct TailHdr {               // device side, zeroed before every run with a host tail
+  uint64_t count;              // chunks taken (k_offload_cut's plan; k_offload_take fills it)
+  uint64_t cutb;               // buckets >= cutb are taken (kTailBuckets: none)
+  uint64_t bytes;              // ring bytes of the plan
+  uint64_t blocks;             // SHA-256 blocks of the plan
+  uint64_t mx_all;             // the run's longest job before the cut
+  uint64_t mx_left;            // ... and after it (Counters::max_nblocks from then on)
+  uint64_t ring_head;          // k_offload_take: ring bytes handed out
+  uint64_t taken;              // k_offload_take: chunks appended
+  uint32_t cnt[kTailBuckets];  // k_offload_hist, per bucket: candidate jobs,
+  uint32_t maxb[kTailBuckets]; //   the longest of them (blocks),
+  uint64_t rbytes[kTailBuckets];  // their ring bytes
+  uint64_t nblk[kTailBuckets];    //   and their blocks
+  uint32_t base[kTailBuckets]; // k_offload_cut: bucket b's first place in the list (longest first)
+  uint32_t fill[kTailBuckets]; // k_offload_take: places handed out
+};
+static_assert(sizeof(TailHdr) % 16 == 0, "TailHdr layout");
+constexpr uint32_t kTailMetaWords = 8;  // pinned: count (kCountUnknown until final), cut blocks,
+                                        // ring bytes, longest before, longest left, blocks
+__host__ __device__ inline uint64_t tail_slot(uint64_t len) {
+  return (len + 16 + kTailSlotAlign - 1) & ~(uint64_t)(kTailSlotAlign - 1);
+}
+
 constexpr uint32_t kLongMinBlocks = 1024;  // never use the wave path below 64 KiB
 #ifndef BSG_SOLO
 #define BSG_SOLO 16  // configs[2]: the 9th-16th longest jobs on group tickets (1.40 us per

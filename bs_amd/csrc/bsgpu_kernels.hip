@@ -2571,9 +2571,19 @@ hipError_t launch_early_fix(Early* e, ChunkRec* out, Counters* ctr, hipStream_t 
   return hipGetLastError();
 }
 
-hipError_t launch_longlist(const ShaArgs& a, uint64_t job_bound, hipStream_t s, int num_cus) {
+hipError_t launch_lens(const ShaArgs& a, uint64_t job_bound, hipStream_t s, int num_cus) {
   const uint32_t grid = grid_for(job_bound, 256, 4u * (uint32_t)num_cus);
   hipLaunchKernelGGL(k_lens, dim3(grid), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_longlist(const ShaArgs& a, uint64_t job_bound, hipStream_t s, int num_cus) {
+  const hipError_t e = launch_lens(a, job_bound, s, num_cus);
+  return e != hipSuccess ? e : launch_order(a, job_bound, s, num_cus);
+}
+
+hipError_t launch_order(const ShaArgs& a, uint64_t job_bound, hipStream_t s, int num_cus) {
+  const uint32_t grid = grid_for(job_bound, 256, 4u * (uint32_t)num_cus);
   hipLaunchKernelGGL(k_thresh, dim3(1), dim3(1), 0, s, a.ctr, a.long_mode);
   hipLaunchKernelGGL(k_order<false>, dim3(grid), dim3(256), 0, s, a);
   hipLaunchKernelGGL(k_bucket_scan, dim3(1), dim3(1024), 0, s, a);
@@ -2618,5 +2628,6 @@ hipError_t launch_sha_blobs(const BlobShaArgs& a, hipStream_t s, int num_cus) {
 #include "bsgpu_gc.inc"
 #include "bsgpu_pool.inc"
 #include "bsgpu_read.inc"
+#include "bsgpu_tail.inc"
 
 }  // namespace bsg

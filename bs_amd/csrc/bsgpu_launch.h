@@ -145,6 +145,39 @@ hipError_t launch_blob_jobs(const ChunkArgs& a, const StreamDesc* streams, uint3
                             hipStream_t s, int num_cus);
 hipError_t launch_sha(const ShaArgs& a, uint64_t job_bound, hipStream_t s, int num_cus);
 hipError_t launch_longlist(const ShaArgs& a, uint64_t job_bound, hipStream_t s, int num_cus);
+// launch_longlist in two parts for a run with a host tail: k_lens, then (after launch_tail_pick
+// took the host's chunks out of jinfo) the ordering kernels
+hipError_t launch_lens(const ShaArgs& a, uint64_t job_bound, hipStream_t s, int num_cus);
+hipError_t launch_order(const ShaArgs& a, uint64_t job_bound, hipStream_t s, int num_cus);
+
+// Host tail (see TailHdr). launch_tail_pick on the run's stream after k_lens; launch_tail_gather
+// on a second stream after it; launch_tail_fix on the run's stream once d_refs holds the host's
+// refs.
+struct TailArgs {
+  uint32_t* jinfo;
+  const LaneJob* jdesc;
+  Counters* ctr;
+  uint64_t chunk_cap;
+  TailHdr* hdr;
+  TailItem* dlist;          // [max_items] device copy of the list
+  uint64_t* dsrc;           // [max_items] the chunks' device addresses
+  uint64_t* hmeta;          // pinned [kTailMetaWords]
+  TailItem* hlist;          // pinned [max_items]
+  uint32_t* hready;         // pinned [max_items]
+  uint8_t* ring;            // pinned
+  uint64_t ring_bytes;
+  uint32_t max_items;
+  uint32_t force_cut;       // > 0: take every job of at least this many blocks that fits
+  float us_per_block;       // cost model: the GPU chain,
+  float pcie_bytes_us;      //   the gather,
+  float host_bytes_us;      //   all hash workers together
+  float host1_bytes_us;     //   and one of them
+  const uint8_t* d_refs;    // [32 * max_items]
+  ChunkRec* out;
+};
+hipError_t launch_tail_pick(const TailArgs& a, uint64_t job_bound, hipStream_t s, int num_cus);
+hipError_t launch_tail_gather(const TailArgs& a, hipStream_t s);
+hipError_t launch_tail_fix(const TailArgs& a, hipStream_t s);
 hipError_t launch_sha_blobs(const BlobShaArgs& a, hipStream_t s, int num_cus);
 // Early chains (see Early): picked and hashed on a second stream from k_compact on (k_lens waits
 // for the picks), the records' fix-up on the engine stream after k_sha (it waits for the chains).

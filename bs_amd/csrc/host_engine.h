@@ -38,6 +38,7 @@ struct RunPlan {
   bool scan = false;       // scan and selection stages (a split run; a hash run has neither)
   bool early = false;      // early chains on a second stream
   bool light = false;      // ... in the lightly loaded arrangement (bsg_engine, "Round 5")
+  bool tail = false;       // host tail (bsg_engine, "Host tail"); then no early chains
 };
 
 // Counters::error after a run
@@ -130,6 +131,47 @@ struct bsg_engine {
     return !snapshot && !hash_mode && knob(BSG_KNOB_EARLY) != 0;
   }
 
+  // Host tail (bsgpu_internal.h, TailHdr): a lightly loaded run of at least tail_min bytes hands
+  // its longest chunks to host threads. k_offload_pick (after k_lens) takes them out of k_sha's
+  // queues, k_offload_gather copies their bytes into a pinned ring on the second stream while
+  // k_sha runs, the workers hash each chunk as its flag rises, and finish() (or the next run)
+  // copies the refs up and launches k_offload_fix. Such a run has no early chains: they start
+  // before the lengths are known and would hold on to the very chunks the host should take, and
+  // k_sha's helped solo tickets run what is then the GPU's longest chains at the same rate.
+  // The ring, the lists and the workers are made at the engine's first such run and kept, so an
+  // engine that never runs one holds neither pinned memory nor threads; that first run pays the
+  // pinned allocation (tens of ms, host_mem.h) and the threads' creation. The workers belong to
+  // the engine: at most 16 threads each, so several engines with tails at once have 16 each.
+  // Runs under 512 MiB keep the early-chain path (256 MiB up) that the parity tests pin there.
+  static constexpr uint64_t kTailMinBytes = 512ull << 20;
+  static constexpr uint64_t kTailRingMax = 256ull << 20;
+  // Cost model constants (k_offload_cut): the solo chain's time per block, profiles/BENCH_r06.json
+  // sha_path.long.us_per_block; the gather's rate, the same file's end_to_end.h2d_busy_gbs (the
+  // link's other direction, measured by the streaming leg).
+  static constexpr float kTailUsPerBlock = 0.95f;
+  static constexpr float kTailPcieBytesUs = 56e3f;
+  uint64_t tail_min = kTailMinBytes;  // test tooling lowers it (bsg_engine_host_tail_debug)
+  uint32_t tail_force_cut = 0;        // ... forces the cut (blocks; 0: the cost model)
+  bool tail_portable = false;         // ... and the portable hash
+  uint64_t tail_ring_force = 0;       // ... and the ring's size (0: by the run's size)
+  std::unique_ptr<HashWorkers> workers;
+  DevBuf tail_hdr, tail_list, tail_src, tail_refs;
+  PinBuf h_tail, h_ring;  // meta, flags, list, refs | the ring
+  Event tail_ev, gather_ev0, gather_ev1;
+  bool tail_open = false;  // a run's tail is under way: its refs are not in the records yet
+  TailArgs tail_args{};
+  int64_t tail_t0_ns = 0;  // when the run was enqueued (steady clock)
+  struct TailStat {
+    uint64_t chunks = 0, bytes = 0, cut = 0, longest_all = 0, longest_left = 0, blocks = 0;
+    float gather_ms = 0.f;
+    int64_t host_done_us = 0;  // the last host hash's end after the run's enqueue
+    int impl = 0, threads = 0;
+    double host_rate = 0;      // one worker's measured bytes per second
+  } tail_stat;
+  bool tail_ok() const {
+    return !snapshot && !hash_mode && knob(BSG_KNOB_HOST_TAIL) != 0;
+  }
+
   uint32_t fanout = 8;        // the last bsg_engine_run's
   bool run_done = false;      // the last enqueue was a bsg_engine_run that finish() completed
   // The passes over a finished split run, each with its own buffers. Trees and restore hash
@@ -190,7 +232,11 @@ struct bsg_engine {
     pl.lists = pl.strips ? scan_lists(pl.strips, num_cus) : 0;
     pl.list_cap = scan_list_cap(pl.strips, pl.lists);
     pl.jobs = pl.chunk_cap + pl.ns;
-    pl.early = early_ok() && pl.total_len >= early_min && pl.strips;
+    // the host tail: lightly loaded runs only (a loaded run's step is its hash work, which the
+    // GPU does faster, not one chain)
+    pl.tail = tail_ok() && pl.total_len >= tail_min && pl.strips &&
+              pl.total_len <= (uint64_t)knob(BSG_KNOB_LIGHT_BYTES).load();
+    pl.early = !pl.tail && early_ok() && pl.total_len >= early_min && pl.strips;
     pl.light = pl.early && pl.total_len <= (uint64_t)knob(BSG_KNOB_LIGHT_BYTES).load();
     return pl;
   }
@@ -463,8 +509,150 @@ struct bsg_engine {
     return BSG_OK;
   }
 
+  // One worker's SHA-256 rate (bytes per second), measured once per process for about a
+  // millisecond on a resident buffer: bsg_init's warm-up, or the first run with a host tail.
+  static double host_sha_rate(bool portable) {
+    static const double best = sha256_measure_rate(sha256_best_impl(), 256 << 10, 1.0);
+    if (!portable || sha256_best_impl() == kShaPortable) return best;
+    static const double plain = sha256_measure_rate(kShaPortable, 256 << 10, 1.0);
+    return plain;
+  }
+
+  // the workers, the second stream, the ring and the lists of a run with a host tail
+  int tail_prepare(const RunPlan& pl) {
+    if (!workers) workers.reset(new (std::nothrow) HashWorkers());
+    if (!workers) return BSG_ENOMEM;
+    if (!estream) HCHECK(stream_acquire(dev, &estream));
+    HCHECK(tail_ev.create(hipEventDisableTiming | hipEventDisableSystemFence));
+    HCHECK(gather_ev0.create());
+    HCHECK(gather_ev1.create());
+    const uint64_t ring =
+        tail_ring_force ? tail_ring_force
+                        : std::min<uint64_t>(kTailRingMax, std::max<uint64_t>(1 << 20, pl.total_len / 8));
+    const uint32_t items = kTailMaxItems;
+    HCHECK(h_ring.ensure(ring));
+    const size_t meta = 64, flags = 4ull * items, list = sizeof(TailItem) * items;
+    HCHECK(h_tail.ensure(meta + flags + list + 32ull * items));
+    HCHECK(tail_hdr.ensure(sizeof(TailHdr)));
+    HCHECK(tail_list.ensure(sizeof(TailItem) * items));
+    HCHECK(tail_src.ensure(8ull * items));
+    HCHECK(tail_refs.ensure(32ull * items));
+    uint8_t* hd = static_cast<uint8_t*>(h_tail.dev());
+    uint8_t* rd = static_cast<uint8_t*>(h_ring.dev());
+    if (!hd || !rd) return BSG_EDEVICE;
+    TailArgs& a = tail_args;
+    a = TailArgs{};
+    a.jinfo = jinfo.as<uint32_t>();
+    a.jdesc = jdesc.as<LaneJob>();
+    a.ctr = dctr();
+    a.chunk_cap = pl.chunk_cap;
+    a.hdr = tail_hdr.as<TailHdr>();
+    a.dlist = tail_list.as<TailItem>();
+    a.dsrc = tail_src.as<uint64_t>();
+    a.hmeta = reinterpret_cast<uint64_t*>(hd);
+    a.hready = reinterpret_cast<uint32_t*>(hd + meta);
+    a.hlist = reinterpret_cast<TailItem*>(hd + meta + flags);
+    a.ring = rd;
+    a.ring_bytes = ring;
+    a.max_items = items;
+    a.force_cut = tail_force_cut;
+    const double r1 = host_sha_rate(tail_portable);
+    a.us_per_block = kTailUsPerBlock;
+    a.pcie_bytes_us = kTailPcieBytesUs;
+    a.host1_bytes_us = (float)(r1 * 1e-6);
+    a.host_bytes_us = (float)(r1 * 1e-6 * workers->threads());
+    a.d_refs = tail_refs.as<uint8_t>();
+    a.out = out.as<ChunkRec>();
+    tail_stat = TailStat{};
+    tail_stat.host_rate = r1;
+    tail_stat.threads = workers->threads();
+    tail_stat.impl = tail_portable ? (int)kShaPortable : sha256_best_impl();
+    return BSG_OK;
+  }
+
+  // after k_lens: the host's chunks out of the queues
+  int run_tail_pick(const RunPlan& pl, hipStream_t s) {
+    uint8_t* hp = h_tail.as<uint8_t>();
+    uint64_t* meta = reinterpret_cast<uint64_t*>(hp);
+    std::memset(hp, 0, 64 + 4ull * tail_args.max_items);
+    meta[0] = kCountUnknown;
+    HCHECK(hipMemsetAsync(tail_hdr.p, 0, sizeof(TailHdr), s));
+    HCHECK(dbg("launch_tail_pick", s, launch_tail_pick(tail_args, pl.jobs, s, num_cus)));
+    return BSG_OK;
+  }
+
+  // After the ordering kernels, beside k_sha: the gather on the second stream, the workers
+  // started on the (still empty) list. Beside the ordering kernels instead, the gather's writes,
+  // which leave at the link's rate, held up theirs: k_order's scatter pass took 0.94 ms for
+  // ~10 us and k_bucket_scan 0.33 ms for 16 us (rocprofv3 kernel trace of that arrangement), all
+  // of it in front of k_sha. k_sha writes next to nothing while it hashes.
+  int run_tail_gather(hipStream_t s) {
+    uint8_t* hp = h_tail.as<uint8_t>();
+    uint64_t* meta = reinterpret_cast<uint64_t*>(hp);
+    HCHECK(hipEventRecord(tail_ev, s));
+    HCHECK(hipStreamWaitEvent(estream, tail_ev, 0));
+    HCHECK(hipEventRecord(gather_ev0, estream));
+    HCHECK(dbg("launch_tail_gather", estream, launch_tail_gather(tail_args, estream)));
+    HCHECK(hipEventRecord(gather_ev1, estream));
+    static_assert(sizeof(HashItem) == sizeof(TailItem), "the list is the workers' items");
+    HashBatch b;
+    b.count = meta;
+    b.ready = reinterpret_cast<const uint32_t*>(hp + 64);
+    b.items = reinterpret_cast<const HashItem*>(hp + 64 + 4ull * tail_args.max_items);
+    b.base = h_ring.as<uint8_t>();
+    b.base_len = tail_args.ring_bytes;
+    b.max_items = tail_args.max_items;
+    b.refs = hp + 64 + (4ull + sizeof(TailItem)) * tail_args.max_items;
+    b.impl = tail_stat.impl;
+    tail_t0_ns = std::chrono::duration_cast<std::chrono::nanoseconds>(
+                     std::chrono::steady_clock::now().time_since_epoch()).count();
+    workers->start(b);
+    tail_open = true;
+    return BSG_OK;
+  }
+
+  // The open tail to its end: the gather done, every chunk hashed, the refs on the device and
+  // k_offload_fix enqueued on the engine stream (behind the run's k_sha).
+  int tail_settle() {
+    if (!tail_open) return BSG_OK;
+    tail_open = false;
+    if (stream_wait(estream) != hipSuccess) {  // the list may never become final
+      (void)hipGetLastError();
+      workers->cancel();
+      (void)workers->wait();
+      return BSG_EDEVICE;
+    }
+    const uint64_t bad = workers->wait();
+    const uint64_t* meta = h_tail.as<uint64_t>();
+    const uint64_t n = std::min<uint64_t>(meta[0], tail_args.max_items);
+    tail_stat.chunks = n;
+    tail_stat.cut = n ? meta[1] : 0;
+    tail_stat.bytes = n ? meta[2] : 0;
+    tail_stat.longest_all = meta[3];
+    tail_stat.longest_left = meta[4];
+    tail_stat.blocks = n ? meta[5] : 0;
+    if (hipEventElapsedTime(&tail_stat.gather_ms, gather_ev0, gather_ev1) != hipSuccess) {
+      (void)hipGetLastError();
+      tail_stat.gather_ms = -1.f;
+    }
+    tail_stat.host_done_us = n ? (workers->last_done_ns() - tail_t0_ns) / 1000 : 0;
+    if (bad || workers->hashed_items() != n) return device_error(64);
+    if (n) {
+      const uint8_t* refs = h_tail.as<uint8_t>() + 64 + (4ull + sizeof(TailItem)) * tail_args.max_items;
+      HCHECK(hipMemcpyAsync(tail_refs.p, refs, 32 * n, hipMemcpyHostToDevice, stream));
+      HCHECK(dbg("launch_tail_fix", stream, launch_tail_fix(tail_args, stream)));
+    }
+    return BSG_OK;
+  }
+
   // the job lists (k_lens .. k_order), then k_sha
   int run_sha(const RunPlan& pl, const ShaArgs& sh, hipStream_t s) {
+    if (pl.tail) {
+      HCHECK(dbg("launch_lens", s, launch_lens(sh, pl.jobs, s, num_cus)));
+      if (int rc = run_tail_pick(pl, s)) return rc;
+      HCHECK(dbg("launch_order", s, launch_order(sh, pl.jobs, s, num_cus)));
+      if (int rc = run_tail_gather(s)) return rc;
+    } else
     HCHECK(dbg("launch_longlist", s, launch_longlist(sh, pl.jobs, s, num_cus)));
     mark(2, s);
     HCHECK(dbg("launch_sha", s, launch_sha(sh, pl.jobs, s, num_cus)));
@@ -490,9 +678,14 @@ struct bsg_engine {
       HCHECK(hipStreamSynchronize(estream));
       early_open = false;
     }
+    // a run enqueued behind one that was not finished: that one's tail first (its refs go into
+    // the records this run is about to overwrite, in stream order)
+    if ((rc = tail_settle())) return rc;
     const RunPlan pl = plan_split();
     if ((rc = reserve(pl)) || (rc = run_start(pl, stream))) return rc;
     if (pl.early && (rc = early_prepare())) return rc;
+    if (pl.tail && (rc = tail_prepare(pl))) return rc;
+    if (!pl.tail) tail_stat = TailStat{};
     const ShaArgs sh = sha_args(pl, long_mode(), pl.early ? dearly() : nullptr);
     if ((rc = run_scan(pl, stream))) return rc;
     hipStream_t sel_stream = stream;  // where selection and k_sha run
@@ -514,6 +707,10 @@ struct bsg_engine {
     run_done = false;
     dd.valid = false;  // a dedup result belongs to the run it was made from
     tree.valid = false;  // ... and so does a tree (bsg_engine_pool_put reads both)
+    // behind a split run that was not finished: that run's tail first, while its records and
+    // lists still stand (reserve may move them); its fix lands before this run in stream order
+    if ((rc = tail_settle())) return rc;
+    tail_stat = TailStat{};  // a hash run has no tail
     const RunPlan pl = plan_hash();
     if ((rc = reserve(pl)) || (rc = run_start(pl, stream))) return rc;
     mark(0);
@@ -531,6 +728,10 @@ struct bsg_engine {
   int finish(uint64_t* nchunks) {
     if (!enqueued) return BSG_ESTATE;
     for (int attempt = 0; attempt < 3; ++attempt) {
+      if (int rc = tail_settle()) {
+        enqueued = false;
+        return rc;
+      }
       HCHECK(hipMemcpyAsync(h_ctr.p, ctr.p, sizeof(Counters), hipMemcpyDeviceToHost, stream));
       HCHECK(stream_wait(stream));
       last = *h_ctr.as<Counters>();

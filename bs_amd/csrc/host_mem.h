@@ -323,6 +323,10 @@ std::atomic<int64_t>& knob(int k) {
     return e ? (int64_t)(std::strtoull(e, nullptr, 10) != 0) : (int64_t)1;
   }()};
   static std::atomic<int64_t> light_bytes{(int64_t)(4ull << 30)};  // engine runs: light schedule
+  static std::atomic<int64_t> host_tail{[] {  // host tail (bsg_engine): 1 on, 0 off
+    const char* e = std::getenv("BSG_HOST_TAIL");
+    return e ? (int64_t)(std::strtoull(e, nullptr, 10) != 0) : (int64_t)1;
+  }()};
   static std::atomic<int64_t> none{0};
   switch (k) {
     case BSG_KNOB_SEQ_WAIT: return seq_wait;
@@ -332,6 +336,7 @@ std::atomic<int64_t>& knob(int k) {
     case BSG_KNOB_POLL: return poll;
     case BSG_KNOB_COPY_NT: return copy_nt;
     case BSG_KNOB_LIGHT_BYTES: return light_bytes;
+    case BSG_KNOB_HOST_TAIL: return host_tail;
     default: return none;
   }
 }

@@ -735,6 +735,17 @@ int bsg_engine_stage_ms(const bsg_engine* eng, float out[3]);
  * start/end (100 MHz) and block count, [8..12] the same for the longest per-lane job,
  * [13] per-lane job count. */
 int bsg_engine_diag(const bsg_engine* eng, uint64_t out[16]);
+/* The host tail of the last finished run (BSG_KNOB_HOST_TAIL): a run of 512 MiB to
+ * BSG_KNOB_LIGHT_BYTES may hash its longest chunks on up to 16 host threads while the GPU hashes
+ * the rest; the data and the records stay in device memory, those chunks' bytes cross the link
+ * once. [0] chunks and [1] ring bytes handed to the host (0: none, or no such run), [2] the cut
+ * in SHA-256 blocks, [3] the gather kernel's time in us (HIP events), [4] the last host hash's
+ * end in us after the run was enqueued, [5] the implementation (0 portable, 1 x86 SHA
+ * extensions), [6] worker threads, [7] one worker's measured rate in bytes/s, [8] the run's
+ * longest chunk in blocks and [9] the longest left on the GPU, [10] blocks hashed on the host,
+ * [11] 1 if cpuid reports the SHA extensions. With a tail, bsg_engine_diag's longest job and
+ * block total are those of the GPU's share. */
+int bsg_engine_host_tail(const bsg_engine* eng, uint64_t out[12]);
 /* Diagnostic timeline of the last run's k_sha, in 100 MHz s_memrealtime ticks: first wave
  * started, longest wave-mode job started / ended, last wave left per-lane mode. */
 int bsg_engine_timeline(const bsg_engine* eng, uint64_t out[4]);
@@ -878,7 +889,10 @@ void bsg_reader_free(bsg_reader* r);
                                   * their early chains on the engine stream and move selection
                                   * and k_sha to the second stream; larger runs the other way
                                   * (tests run one input both ways) */
-#define BSG_KNOB_LAST BSG_KNOB_LIGHT_BYTES
+#define BSG_KNOB_HOST_TAIL 8    /* BSG_HOST_TAIL: 1 (default) lets an engine run of 512 MiB to
+                                  * BSG_KNOB_LIGHT_BYTES hash its longest chunks on host threads
+                                  * (bsg_engine_host_tail); 0 keeps every chunk on the GPU */
+#define BSG_KNOB_LAST BSG_KNOB_HOST_TAIL
 int bsg_debug_set(int knob, int64_t value);
 int64_t bsg_debug_get(int knob); /* -1 for an unknown knob */
 
