@@ -168,6 +168,23 @@ class PoolCollectInfo(ctypes.Structure):
 
 
 assert ctypes.sizeof(PoolCollectInfo) == 88
+MERGE_ALL = 2          # BSG_MERGE_ALL (Engine.pool_merge)
+MERGE_VERIFY = 4       # BSG_MERGE_VERIFY (Engine.pool_merge, Engine.pool_sync)
+
+
+class PoolMergeInfo(ctypes.Structure):
+    """bsg_pool_merge_info (include/bsgpu.h)."""
+    _fields_ = [("gc", GcInfo)] + [(k, ctypes.c_uint64) for k in
+                                   ("selected", "added", "added_bytes", "known", "first_blob",
+                                    "need_bytes", "need_blobs", "bad_blob", "verified")]
+
+    def as_dict(self) -> dict:
+        d = {k: int(getattr(self, k)) for k, _ in self._fields_[1:]}
+        d["gc"] = self.gc.as_dict()
+        return d
+
+
+assert ctypes.sizeof(PoolMergeInfo) == 144
 READ_VERIFY = 1        # BSG_READ_VERIFY (Engine.read, Pool.read)
 READ_RANGE_DTYPE = np.dtype([("root", "u1", (32,)), ("offset", "<u8"), ("len", "<u8")])
 assert READ_RANGE_DTYPE.itemsize == 48
@@ -325,6 +342,11 @@ def lib() -> ctypes.CDLL:
         "bsg_pool_kill_debug": (ctypes.c_int, [vp]),
         "bsg_engine_read_ms_debug": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_float)]),
         "bsg_pool_collect_ms_debug": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_float)]),
+        "bsg_pool_merge": (ctypes.c_int, [vp, vp, vp, vp, ctypes.c_uint64, ctypes.c_int, vp,
+                                          ctypes.POINTER(PoolMergeInfo)]),
+        "bsg_pool_sync": (ctypes.c_int, [vp, vp, vp, ctypes.c_int, ctypes.POINTER(PoolMergeInfo)]),
+        "bsg_pool_merge_ms_debug": (ctypes.c_int, [vp, ctypes.c_int,
+                                                   ctypes.POINTER(ctypes.c_float)]),
         "bsg_engine_pack_mode_debug": (ctypes.c_int, [vp, ctypes.c_int]),
         "bsg_engine_d2d_ms_debug": (ctypes.c_int, [vp, vp, vp, ctypes.c_uint64,
                                                    ctypes.POINTER(ctypes.c_float)]),
@@ -948,6 +970,57 @@ class Engine:
         if rc == BSG_OK:
             dst._nremap = nsrc
         return rc, info.as_dict(), status[:nr]
+
+    def pool_merge(self, src: "Pool", dst: "Pool", roots=None, all: bool = False,
+                   verify: bool = False, missing_leaves: bool = False):
+        """bsg_pool_merge: the blobs of `src` that are live from `roots` (every blob with
+        all=True, which takes no roots) and whose refs `dst` lacks, appended to `dst`. Returns
+        (rc, info, status) like pool_collect: the bsg_pool_merge_info as a dict and the per-Root
+        status; a negative rc is returned, not raised. Without all=True the mark is this engine's
+        gc result afterwards; dst.remap() serves the remap."""
+        if roots is None:
+            rp, nr = None, 0
+        else:
+            roots = np.ascontiguousarray(np.frombuffer(roots, dtype=np.uint8)
+                                         if isinstance(roots, (bytes, bytearray)) else roots,
+                                         dtype=np.uint8).reshape(-1)
+            assert len(roots) % 32 == 0
+            rp, nr = roots.ctypes.data, len(roots) // 32
+        flags = ((MERGE_ALL if all else 0) | (MERGE_VERIFY if verify else 0)
+                 | (GC_MISSING_LEAVES if missing_leaves else 0))
+        status = np.zeros(max(nr, 1), dtype=np.int32)
+        info = PoolMergeInfo()
+        nsrc = src.stat()["nblobs"] if src is not None and src.h else 0
+        rc = lib().bsg_pool_merge(self.h, src.h if src is not None else None,
+                                  dst.h if dst is not None else None, rp, nr, flags,
+                                  status.ctypes.data, ctypes.byref(info))
+        if not all:
+            self._gc_nblobs, self._gc_nlive = nsrc, int(info.gc.nlive)
+        if rc == BSG_OK:
+            dst._nremap = nsrc
+        return rc, info.as_dict(), status[:nr]
+
+    def pool_sync(self, a: "Pool", b: "Pool", verify: bool = False):
+        """bsg_pool_sync: afterwards `a` and `b` hold the same set of refs. Returns (rc, info,
+        status): info is the two directions' bsg_pool_merge_info ([0]: a -> b, [1]: b -> a) as
+        dicts, status an empty array (no Roots are involved); a negative rc is returned, not
+        raised. b.remap() covers a's blobs at the call, a.remap() b's."""
+        info = (PoolMergeInfo * 2)()
+        na = a.stat()["nblobs"] if a is not None and a.h else 0
+        nb = b.stat()["nblobs"] if b is not None and b.h else 0
+        rc = lib().bsg_pool_sync(self.h, a.h if a is not None else None,
+                                 b.h if b is not None else None, MERGE_VERIFY if verify else 0,
+                                 info)
+        if rc == BSG_OK:
+            b._nremap, a._nremap = na, nb
+        return rc, [info[0].as_dict(), info[1].as_dict()], np.zeros(0, dtype=np.int32)
+
+    def pool_merge_ms(self, direction: int = 0) -> dict:
+        """The last pool_merge (direction 0) or a direction of the last pool_sync on this engine,
+        in ms (test tooling; needs profile() on)."""
+        out = (ctypes.c_float * 5)()
+        _check(lib().bsg_pool_merge_ms_debug(self.h, direction, out), "bsg_pool_merge_ms_debug")
+        return dict(zip(("probe", "plan", "verify", "append", "gather"), map(float, out)))
 
     def pool_walk(self, pool: "Pool", roots, flags: int = 0):
         """bsg_pool_walk: walk() on a bsg_pool where it lies (its device table and index).

@@ -655,6 +655,92 @@ int bsg_pool_collect(bsg_engine* e, bsg_pool* src, bsg_pool* dst, const uint8_t*
   return dst->collect(e->view(), e->gc, *src, roots, nroots, flags, status, info);
 }
 
+// ---- a pool merged into a pool that holds something; two pools synced --------------------------
+static_assert(sizeof(bsg_pool_merge_info) == 144, "bsg_pool_merge_info layout");
+
+static bsg_pool_merge_info merge_clear(bool all) {
+  bsg_pool_merge_info i{};
+  if (!all) i.gc.bad_root = i.gc.bad_blob = UINT64_MAX;
+  i.bad_blob = UINT64_MAX;
+  return i;
+}
+
+int bsg_pool_merge(bsg_engine* e, bsg_pool* src, bsg_pool* dst, const uint8_t* roots,
+                   uint64_t nroots, int flags, int32_t* status, bsg_pool_merge_info* info) {
+  bsg_pool_merge_info none{};
+  if (!info) info = &none;
+  const bool all = (flags & BSG_MERGE_ALL) != 0;
+  *info = merge_clear(all);
+  if (!e || !src || !dst || src == dst || src->dev != e->dev || dst->dev != e->dev ||
+      (flags & ~(BSG_GC_MISSING_LEAVES | BSG_MERGE_ALL | BSG_MERGE_VERIFY)) ||
+      (all && (roots || nroots || (flags & BSG_GC_MISSING_LEAVES))) || nroots > 0xffffffffull ||
+      (!roots && nroots))
+    return BSG_EINVAL;
+  // both pools for the whole call, taken together, as bsg_pool_collect
+  std::unique_lock<std::mutex> gs(src->mu, std::defer_lock), gd(dst->mu, std::defer_lock);
+  std::lock(gs, gd);
+  if (src->dead || dst->dead || e->enqueued) return BSG_ESTATE;
+  int rc = e->setdev();
+  if (rc) return rc;
+  const RunView v = e->view();
+  const uint8_t* sel = nullptr;
+  if (!all) {
+    const PoolSrc ps = src->source();
+    rc = e->gc.mark(v, src->bytes.as<const uint8_t>(), src->pool_bytes(), nullptr, src->nblobs,
+                    roots, nroots, flags & BSG_GC_MISSING_LEAVES, status, &info->gc, &ps);
+    if (rc) return rc;
+    sel = e->gc.live.as<const uint8_t>();
+  }
+  MergeWork& w = e->merge[0];
+  if ((rc = w.plan(v, *src, *dst, sel, info))) return rc;
+  if ((flags & BSG_MERGE_VERIFY) && (rc = w.verify(v, *src, info))) return rc;
+  if (!w.fits(*dst, *info)) return BSG_ENOMEM;
+  return w.commit(v, *src, *dst);
+}
+
+int bsg_pool_sync(bsg_engine* e, bsg_pool* a, bsg_pool* b, int flags, bsg_pool_merge_info info[2]) {
+  bsg_pool_merge_info none[2];
+  if (!info) info = none;
+  info[0] = info[1] = merge_clear(true);
+  if (!e || !a || !b || a == b || a->dev != e->dev || b->dev != e->dev ||
+      (flags & ~BSG_MERGE_VERIFY))
+    return BSG_EINVAL;
+  std::unique_lock<std::mutex> ga(a->mu, std::defer_lock), gb(b->mu, std::defer_lock);
+  std::lock(ga, gb);
+  if (a->dead || b->dead || e->enqueued) return BSG_ESTATE;
+  int rc = e->setdev();
+  if (rc) return rc;
+  const RunView v = e->view();
+  // What b lacks of a and what a lacks of b, each against the other pool as it stands: a blob the
+  // first direction appends to b is one a holds, so the second direction would find it known.
+  bsg_pool* src[2] = {a, b};
+  bsg_pool* dst[2] = {b, a};
+  for (int d = 0; d < 2; ++d)
+    if ((rc = e->merge[d].plan(v, *src[d], *dst[d], nullptr, &info[d]))) return rc;
+  int corrupt = BSG_OK;  // (both directions are verified, so both infos are filled)
+  for (int d = 0; d < 2 && (flags & BSG_MERGE_VERIFY); ++d) {
+    if ((rc = e->merge[d].verify(v, *src[d], &info[d])) == BSG_ECORRUPT) corrupt = rc;
+    else if (rc) return rc;
+  }
+  if (corrupt) return corrupt;
+  for (int d = 0; d < 2; ++d)
+    if (!e->merge[d].fits(*dst[d], info[d])) return BSG_ENOMEM;
+  // (the second append reads a's blobs below its old end and writes behind it)
+  for (int d = 0; d < 2; ++d)
+    if ((rc = e->merge[d].commit(v, *src[d], *dst[d]))) return rc;
+  return BSG_OK;
+}
+
+// Test and measurement tooling (not in bsgpu.h): the last bsg_pool_merge on e (dir 0), or a
+// direction of its last bsg_pool_sync: the probe, the plan, the verification, k_pool_merge_append
+// and the gather in ms, timed with HIP events on the engine's stream when bsg_engine_profile is on
+// (else zeros).
+extern "C" int bsg_pool_merge_ms_debug(const bsg_engine* e, int dir, float out[5]) {
+  if (!e || !out || dir < 0 || dir > 1) return BSG_EINVAL;
+  for (int i = 0; i < 5; ++i) out[i] = e->merge[dir].ms[i];
+  return BSG_OK;
+}
+
 int bsg_pool_copy_remap(bsg_pool* p, uint64_t* remap, uint64_t cap) {
   if (!p || (!remap && cap)) return BSG_EINVAL;
   std::lock_guard<std::mutex> g(p->mu);

@@ -365,4 +365,21 @@ struct PoolHdr {               // one put's totals, read back by the host before
 };
 static_assert(sizeof(PoolHdr) % 16 == 0 && offsetof(PoolHdr, zero) % 16 == 0, "PoolHdr layout");
 
+// A pool's selected blobs appended to a pool that may hold some of them (bsg_pool_merge,
+// bsg_pool_sync; bsgpu_pool.inc). One direction's verdicts and totals, read back by the host
+// before anything of the destination is written.
+struct MergeHdr {
+  GcHdr g;                     // the segment gather's header (g.w.dd.error: the bug guard of the
+                               //   probe, the plan, the append and the gather; g.zero: padding)
+  RestoreHdr r;                // the verification's (r.dd.error: its bug guard; r.invalid bit 4;
+                               //   r.bad_blob: the smallest new blob that does not hash to its ref)
+  uint64_t selected;           // selected blobs of the source
+  uint64_t known;              // ... whose ref the destination held
+  uint64_t added_bytes;        // the new blobs' lens, summed
+  uint64_t end;                // the end of the last new blob's bytes, from the base
+  uint64_t verified;           // the hashed blobs' lens, summed
+  uint64_t pad_;
+};
+static_assert(sizeof(MergeHdr) % 16 == 0 && offsetof(MergeHdr, r) % 16 == 0, "MergeHdr layout");
+
 }  // namespace bsg

@@ -481,6 +481,42 @@ struct AdoptArgs {
 };
 hipError_t launch_pool_adopt(const AdoptArgs& a, hipStream_t s, int num_cus);
 
+// bsg_pool_merge / bsg_pool_sync (bsgpu_pool.inc): the selected blobs of a source pool that the
+// destination's index does not hold, appended behind what the destination holds. src .. index_mask
+// are the two pools as they stand, isnew .. hdr belong to the call; launch_pool_probe and
+// launch_pool_merge_plan write those alone and read nothing from nnew on. nnew and need_bytes are
+// known after the host has read the totals back; launch_pool_merge_append runs only once it has
+// held them to the destination's capacity. New blob k becomes entry dn + rank[k] =
+// {base + off16[k], len, ref} and enters the index; remap[k] is the destination's entry under k's
+// ref, or ~0 for an unselected blob. The bytes are launch_gc_compact's, with isnew as its live[],
+// off16 as its offsets and the destination's bytes + base as its output.
+struct MergeArgs {
+  const PoolBlob* src;       // [n] the source's table
+  uint64_t n;
+  const uint8_t* sel;        // [n] a mark's live[] (null: every blob is selected)
+  const PoolBlob* dtable;    // [dn] the destination's table before the call
+  uint64_t dn;
+  uint64_t* index;           // [index_mask + 1] the destination's blob indices by ref
+  uint64_t index_mask;
+  uint8_t* isnew;            // [n] selected, and the destination lacks its ref
+  uint64_t* rank;            // [n + 1] exclusive prefix of isnew
+  uint64_t* off16;           // [n + 1] ... of the new blobs' lens rounded up to 16
+  uint64_t* part;            // [sum_parts(n)] workgroup sums of a prefix pass
+  uint64_t* remap;           // [n]
+  MergeHdr* hdr;
+  uint64_t nnew;             // rank[n]
+  uint64_t base;             // where the first new blob starts (a multiple of 16)
+  uint64_t need_bytes;       // the end of the last new blob's bytes, in the destination
+  uint64_t cap_blobs;        // the destination's table entries
+  PoolBlob* table;           // the destination's table
+};
+// every selected blob probed in the destination's index: remap, isnew and the header's counts
+hipError_t launch_pool_probe(const MergeArgs& a, hipStream_t s, int num_cus);
+// rank and off16 over the source's blobs, then the end of the last new blob's bytes
+hipError_t launch_pool_merge_plan(const MergeArgs& a, hipStream_t s, int num_cus);
+// the new table entries, their index slots and their remap entries
+hipError_t launch_pool_merge_append(const MergeArgs& a, hipStream_t s, int num_cus);
+
 // bsg_engine_read (bsgpu_read.inc): byte ranges of streams out of a pool. The walk is
 // bsg_engine_walk's with WalkArgs::win set (launch_walk_roots / _count / _emit), the scatter
 // bsg_engine_restore's with RestoreArgs::win0 set (launch_restore_scatter); what lies between is here.

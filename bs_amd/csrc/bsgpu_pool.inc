@@ -175,7 +175,115 @@ __global__ __launch_bounds__(256) void k_pool_adopt(AdoptArgs a) {
   }
 }
 
+// ---- merge: a pool's selected blobs behind what another pool holds (bsg_pool_merge) -------------
+// A pool's refs are pairwise distinct, so which blobs are new is one read-only probe of the
+// destination's index per selected blob; nothing here needs a first-occurrence pass. The probe and
+// the plan write the call's own buffers only. DESIGN §4.15.
+__device__ __forceinline__ void mg_add(uint64_t* w, uint64_t v) {  // one atomic per wave
+  for (int o = 32; o > 0; o >>= 1) v += (uint64_t)__shfl_down((unsigned long long)v, o);
+  if ((threadIdx.x & 63) == 0 && v)
+    atomicAdd(reinterpret_cast<unsigned long long*>(w), (unsigned long long)v);
+}
+
+__global__ __launch_bounds__(256) void k_pool_probe(MergeArgs a) {
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  DedupHdr* eh = &a.hdr->g.w.dd;
+  uint64_t selected = 0, known = 0, bytes = 0;
+  for (uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; k < a.n; k += stride) {
+    uint64_t to = ~0ull;
+    uint8_t fresh = 0;
+    if (!a.sel || a.sel[k]) {
+      ++selected;
+      to = pool_lookup(a.dtable, a.dn, a.index, a.index_mask,
+                       reinterpret_cast<const uint64_t*>(a.src[k].ref), eh);
+      if (to == kDedupEmpty) {  // (its entry is the append's to name)
+        fresh = 1;
+        bytes += a.src[k].len;
+      } else {
+        ++known;
+      }
+    }
+    a.remap[k] = to;
+    a.isnew[k] = fresh;
+  }
+  mg_add(&a.hdr->selected, selected);
+  mg_add(&a.hdr->known, known);
+  mg_add(&a.hdr->added_bytes, bytes);
+}
+
+struct MvNew {
+  __device__ uint64_t operator()(const MergeArgs& a, uint64_t k) const { return a.isnew[k] ? 1 : 0; }
+};
+struct MvLen16 {
+  __device__ uint64_t operator()(const MergeArgs& a, uint64_t k) const {
+    return a.isnew[k] ? align16(a.src[k].len) : 0;
+  }
+};
+
+// the end of the last new blob's bytes (the offsets ascend, so the largest), as k_gc_offsets; a
+// wave takes the largest of its lanes first and adds one atomic
+__global__ __launch_bounds__(256) void k_pool_merge_end(MergeArgs a) {
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  uint64_t end = 0;
+  for (uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; k < a.n; k += stride)
+    if (a.isnew[k]) end = max(end, a.off16[k] + a.src[k].len);
+  for (int o = 32; o > 0; o >>= 1)
+    end = max(end, (uint64_t)__shfl_down((unsigned long long)end, o));
+  if ((threadIdx.x & 63) == 0 && end)
+    atomicMax(reinterpret_cast<unsigned long long*>(&a.hdr->end), (unsigned long long)end);
+}
+
+// New blob k becomes entry dn + rank[k] at base + off16[k], the place launch_gc_compact (live =
+// isnew, coff = off16, out = the destination's bytes + base) gives its bytes. Neither pool holds a
+// ref twice and the destination lacks every new one, so an entry claims the first free slot of its
+// probe sequence and no key is compared, as k_pool_append and k_pool_adopt.
+__global__ __launch_bounds__(256) void k_pool_merge_append(MergeArgs a) {
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  DedupHdr* eh = &a.hdr->g.w.dd;
+  SetArgs ix{};
+  ix.tab = a.index;
+  ix.mask = a.index_mask;
+  ix.hdr = eh;
+  for (uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; k < a.n; k += stride) {
+    if (!a.isnew[k]) continue;
+    const uint64_t j = a.rank[k], len = a.src[k].len, o = a.off16[k];
+    if (j >= a.nnew || a.dn + j >= a.cap_blobs || o % 16 || a.base > a.need_bytes ||
+        o > a.need_bytes - a.base || len > a.need_bytes - a.base - o) {
+      dd_error(eh, 1 << 15);
+      continue;
+    }
+    const uint64_t* r = reinterpret_cast<const uint64_t*>(a.src[k].ref);
+    uint64_t* e = reinterpret_cast<uint64_t*>(a.table + a.dn + j);
+    e[0] = a.base + o;
+    e[1] = len;
+    for (int w = 0; w < 4; ++w) e[2 + w] = r[w];
+    set_insert(ix, r[0], a.dn + j);
+    a.remap[k] = a.dn + j;
+  }
+}
+
 // ---- launchers --------------------------------------------------------------------------------
+hipError_t launch_pool_probe(const MergeArgs& a, hipStream_t s, int num_cus) {
+  if (!a.n) return hipSuccess;
+  hipLaunchKernelGGL(k_pool_probe, dim3(engine_grid(a.n, num_cus)), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_pool_merge_plan(const MergeArgs& a, hipStream_t s, int num_cus) {
+  if (!a.n) return hipSuccess;
+  hipError_t e;
+  if ((e = launch_sum<MvNew>(a, a.n, a.rank, s)) != hipSuccess) return e;
+  if ((e = launch_sum<MvLen16>(a, a.n, a.off16, s)) != hipSuccess) return e;
+  hipLaunchKernelGGL(k_pool_merge_end, dim3(engine_grid(a.n, num_cus)), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_pool_merge_append(const MergeArgs& a, hipStream_t s, int num_cus) {
+  if (!a.nnew) return hipSuccess;
+  hipLaunchKernelGGL(k_pool_merge_append, dim3(engine_grid(a.n, num_cus)), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+
 hipError_t launch_pool_adopt(const AdoptArgs& a, hipStream_t s, int num_cus) {
   if (!a.n) return hipSuccess;
   hipLaunchKernelGGL(k_pool_adopt, dim3(engine_grid(a.n, num_cus)), dim3(256), 0, s, a);

@@ -257,3 +257,175 @@ struct bsg_pool {
     return BSG_OK;
   }
 };
+
+// One direction of bsg_pool_merge / bsg_pool_sync: the selected blobs of `src` that `dst` lacks,
+// appended behind what dst holds. The work owns every buffer it writes before the append, the
+// remap included, so plan() and verify() write nothing of either pool and a call can run both
+// directions of a sync that far before it commits either. (The caller holds both mutexes and has
+// checked the states.)
+struct MergeWork {
+  DevBuf hdr, isnew, rank, off16, part, map, tpre, tlist, descs;
+  PinBuf h_hdr;
+  MergeArgs a{};
+  uint64_t added_bytes = 0;
+  Marks marks;                    // profile
+  float ms[5] = {0, 0, 0, 0, 0};  // profile: probe, plan, verify, append, gather
+
+  int readback(hipStream_t s, MergeHdr* h) {
+    return read_header(h_hdr, hdr.p, s, h,
+                       [](const MergeHdr& m) { return m.g.w.dd.error | m.r.dd.error; }, "pool merge");
+  }
+
+  // The probe and the plan. sel: a finished mark's live[] over src's blobs (null: every blob).
+  // info's counts and need_* are filled; whether they fit is fits()'s to say.
+  int plan(const RunView& v, const bsg_pool& src, const bsg_pool& dst, const uint8_t* sel,
+           bsg_pool_merge_info* info) {
+    const hipStream_t s = v.stream;
+    auto stamp = [&](size_t i) { v.profile ? marks.record(i, s) : void(); };
+    for (float& m : ms) m = 0.f;
+    const uint64_t n = src.nblobs;
+    a = MergeArgs{};
+    a.n = n;
+    a.dn = dst.nblobs;
+    a.base = bsg_pool::pad16(dst.used);
+    a.need_bytes = dst.used;
+    added_bytes = 0;
+    info->first_blob = info->need_blobs = dst.nblobs;
+    info->need_bytes = dst.used;
+    MCHECK(map.ensure(8 * n));
+    if (!n) return BSG_OK;
+
+    MCHECK(hdr.ensure(sizeof(MergeHdr)));
+    MCHECK(h_hdr.ensure(sizeof(MergeHdr) + 16));
+    MCHECK(isnew.ensure(n));
+    MCHECK(rank.ensure(8 * (n + 1)));
+    MCHECK(off16.ensure(8 * (n + 1)));
+    MCHECK(part.ensure(8 * sum_parts(n)));
+    a.src = src.table.as<const PoolBlob>();
+    a.sel = sel;
+    a.dtable = dst.table.as<const PoolBlob>();
+    a.index = dst.index.as<uint64_t>();
+    a.index_mask = dst.slots - 1;
+    a.isnew = isnew.as<uint8_t>();
+    a.rank = rank.as<uint64_t>();
+    a.off16 = off16.as<uint64_t>();
+    a.part = part.as<uint64_t>();
+    a.remap = map.as<uint64_t>();
+    a.hdr = hdr.as<MergeHdr>();
+    a.cap_blobs = dst.cap_blobs;
+    a.table = dst.table.as<PoolBlob>();
+
+    stamp(0);
+    HCHECK(hipMemsetAsync(hdr.p, 0, sizeof(MergeHdr), s));
+    HCHECK(hipMemsetAsync(&a.hdr->r.bad_blob, 0xFF, 8, s));
+    HCHECK(dbg("launch_pool_probe", s, launch_pool_probe(a, s, v.num_cus)));
+    stamp(1);
+    HCHECK(dbg("launch_pool_merge_plan", s, launch_pool_merge_plan(a, s, v.num_cus)));
+    stamp(2);
+    // the totals: the header, and the last word of each prefix
+    uint64_t* tot = reinterpret_cast<uint64_t*>(h_hdr.as<uint8_t>() + sizeof(MergeHdr));
+    HCHECK(hipMemcpyAsync(tot, a.rank + n, 8, hipMemcpyDeviceToHost, s));
+    HCHECK(hipMemcpyAsync(tot + 1, a.off16 + n, 8, hipMemcpyDeviceToHost, s));
+    MergeHdr h;
+    if (int rc = readback(s, &h)) return rc;
+    if (v.profile) {
+      ms[0] = marks.ms(0, 1);
+      ms[1] = marks.ms(1, 2);
+    }
+    const uint64_t nnew = tot[0], total16 = tot[1];
+    if (h.selected > n || nnew + h.known != h.selected || h.end > total16 ||
+        total16 - h.end > 15 || total16 % 16 || (nnew == 0 && total16) || h.added_bytes > total16)
+      return BSG_EDEVICE;
+    a.nnew = nnew;
+    added_bytes = h.added_bytes;
+    info->selected = h.selected;
+    info->known = h.known;
+    info->added = nnew;
+    info->added_bytes = h.added_bytes;
+    info->need_blobs = dst.nblobs + nnew;
+    if (nnew) a.need_bytes = info->need_bytes = a.base + h.end;
+    return BSG_OK;
+  }
+
+  // BSG_MERGE_VERIFY: the blobs plan() found new, and no others, hashed and held to their refs
+  // (BSG_READ_VERIFY's passes, with isnew[] in the place of touched[]).
+  int verify(const RunView& v, const bsg_pool& src, bsg_pool_merge_info* info) {
+    const hipStream_t s = v.stream;
+    info->verified = 0;
+    if (!a.nnew) return BSG_OK;
+    MCHECK(tpre.ensure(8 * (a.n + 1)));
+    MCHECK(tlist.ensure(8 * a.nnew));
+    TouchArgs t{};
+    t.r.pool = src.bytes.as<const uint8_t>();
+    t.r.pool_bytes = src.pool_bytes();
+    t.r.blobs = a.src;
+    t.r.nblobs = a.n;
+    t.r.hdr = &a.hdr->r;
+    t.r.touched = a.isnew;
+    t.tpre = tpre.as<uint64_t>();
+    t.tlist = tlist.as<uint64_t>();
+    t.ntouched = a.nnew;
+    t.verified = &a.hdr->verified;
+    t.part = a.part;
+    if (v.profile) marks.record(3, s);
+    HCHECK(dbg("launch_read_touched", s, launch_read_touched(t, s, v.num_cus)));
+    MergeHdr h;
+    int rc;
+    if ((rc = readback(s, &h))) return rc;
+    // (a pool's blobs meet the hash path's layout rules by construction)
+    if (h.r.invalid || h.verified != added_bytes) return BSG_EDEVICE;
+    if ((rc = hash_touched(v, t, descs, src.used))) return rc;
+    if (v.profile) marks.record(4, s);
+    if ((rc = readback(s, &h))) return rc;
+    if (v.profile) ms[2] = marks.ms(3, 4);
+    info->verified = h.verified;
+    info->bad_blob = h.r.bad_blob;
+    return h.r.bad_blob != ~0ull ? BSG_ECORRUPT : BSG_OK;
+  }
+
+  static bool fits(const bsg_pool& dst, const bsg_pool_merge_info& info) {
+    return info.need_blobs <= dst.cap_blobs && info.need_bytes <= dst.cap_bytes &&
+           info.need_bytes >= dst.used;
+  }
+
+  // The append: table entries and index slots, the bytes, the counters and the remap.
+  int commit(const RunView& v, const bsg_pool& src, bsg_pool& dst) {
+    const hipStream_t s = v.stream;
+    if (a.nnew) {
+      GcArgs g{};  // the segment gather of the collect, over the new blobs
+      g.w.pool = src.bytes.as<const uint8_t>();
+      g.w.pool_bytes = src.pool_bytes();
+      g.w.blobs = a.src;
+      g.w.nblobs = a.n;
+      g.g = &a.hdr->g;
+      g.w.hdr = &g.g->w;
+      g.live = a.isnew;
+      g.coff = a.off16;
+      g.total = a.need_bytes - a.base;
+      g.out = dst.bytes.as<uint8_t>() + a.base;
+      if (v.profile) marks.record(5, s);
+      hipError_t e = dbg("launch_pool_merge_append", s, launch_pool_merge_append(a, s, v.num_cus));
+      if (v.profile) marks.record(6, s);
+      if (e == hipSuccess) e = dbg("launch_gc_compact", s, launch_gc_compact(g, s));
+      if (v.profile) marks.record(7, s);
+      MergeHdr h;
+      if (e != hipSuccess || readback(s, &h)) {  // the table, the index or the bytes may be half written
+        (void)hipGetLastError();
+        (void)hipStreamSynchronize(s);
+        dst.dead = true;
+        return BSG_EDEVICE;
+      }
+      if (v.profile) {
+        ms[3] = marks.ms(5, 6);
+        ms[4] = marks.ms(6, 7);
+      }
+    }
+    dst.remap = std::move(map);
+    dst.nremap = a.n;
+    dst.collect_done = true;
+    dst.nblobs += a.nnew;
+    dst.used = a.need_bytes;
+    dst.blob_bytes += added_bytes;
+    return BSG_OK;
+  }
+};

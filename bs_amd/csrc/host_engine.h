@@ -184,6 +184,7 @@ struct bsg_engine {
   WalkWork walk;
   GcWork gc;
   ReadWork read;
+  MergeWork merge[2];  // bsg_pool_merge uses the first, bsg_pool_sync one per direction
   RunView view() {
     return RunView{this, stream, num_cus, profile, run_done, run_done && !snapshot && !hash_mode,
                    enqueued, d_data, &descs, streams.as<StreamDesc>(), nstreams,

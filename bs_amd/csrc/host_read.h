@@ -4,6 +4,23 @@
 
 namespace {
 
+// The hash runs of BSG_READ_VERIFY and BSG_MERGE_VERIFY: the blobs of t.tlist[0 .. t.ntouched)
+// (launch_read_touched's list, its count read back) hashed through the engine's second engine in
+// batches and held to their refs, on v's stream. The smallest failing blob index ends in
+// t.r.hdr->bad_blob; the caller reads its header back. blob_hi: the end of the pool's last blob.
+inline int hash_touched(const RunView& v, const TouchArgs& t, DevBuf& descs, uint64_t blob_hi) {
+  if (!t.ntouched) return BSG_OK;
+  if (int rc = need_hasher(v.owner)) return rc;
+  return hash_batches(
+      v.owner, descs, t.ntouched, t.r.pool, blob_hi, long_mode(),
+      [&](uint64_t b, uint32_t nb, StreamDesc* d) {
+        return launch_read_descs(t, b, nb, d, v.stream, v.num_cus);
+      },
+      [&](uint64_t b, uint32_t nb, const ChunkRec* rec, Counters* ctr) {
+        return launch_read_compare(t, b, nb, rec, ctr, v.stream, v.num_cus);
+      });
+}
+
 // One level of the pruned walk: the walk's, and a leaf node's run of followed children.
 struct ReadLevel {
   WalkLevel w;
@@ -333,18 +350,7 @@ struct ReadWork {
       // the engine hash path's own rules (bsg_engine_hash), for the touched blobs
       if (h.r.invalid || (ntouched && p0 % 16 != 0)) return BSG_EINVAL;
       t.ntouched = ntouched;
-      if (ntouched) {
-        if ((rc = need_hasher(v.owner))) return rc;
-        rc = hash_batches(
-            v.owner, descs, ntouched, d_pool, blob_hi, long_mode(),
-            [&](uint64_t b, uint32_t nb, StreamDesc* d) {
-              return launch_read_descs(t, b, nb, d, stream, v.num_cus);
-            },
-            [&](uint64_t b, uint32_t nb, const ChunkRec* rec, Counters* ctr) {
-              return launch_read_compare(t, b, nb, rec, ctr, stream, v.num_cus);
-            });
-        if (rc) return rc;
-      }
+      if ((rc = hash_touched(v, t, descs, blob_hi))) return rc;
       mark(6);
       if ((rc = readback(stream, &h))) return rc;
       ms[4] = elapsed(5, 6);

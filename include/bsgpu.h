@@ -504,9 +504,9 @@ int bsg_engine_gc_compact(bsg_engine* eng, const uint8_t* d_pool, uint64_t pool_
  * creation, and a table of cap_blobs entries. Neither ever moves, so the device pointers below
  * stay valid for the pool's life and a walk, restore or gc may hold them. The capacity is fixed and
  * the pool only ever grows (no growth past the capacity, no delete of single refs; a pool is
- * collected into another, empty pool with bsg_pool_collect and emptied for reuse with
- * bsg_pool_reset, below). bsg_pool_new returns NULL with BSG_ENODEV (no such device) or BSG_ENOMEM
- * in *err.
+ * collected into another, empty pool with bsg_pool_collect, merged into one that holds something
+ * with bsg_pool_merge and emptied for reuse with bsg_pool_reset, below). bsg_pool_new returns
+ * NULL with BSG_ENODEV (no such device) or BSG_ENOMEM in *err.
  * Layout. Every blob starts at a multiple of 16 and the padding after it (at most 15 bytes) is
  * zero, so the pool (bsg_pool_bytes_device, with pool_bytes of bsg_pool_stat and the table of
  * bsg_pool_copy_table) is at all times a valid argument set for bsg_engine_walk,
@@ -615,6 +615,77 @@ int bsg_pool_collect(bsg_engine* eng, bsg_pool* src, bsg_pool* dst,
  * on a dead pool. */
 int bsg_pool_copy_remap(bsg_pool* dst, uint64_t* remap, uint64_t cap);
 const uint64_t* bsg_pool_remap_device(const bsg_pool* dst);
+
+/* ---- a pool merged into a pool that holds something; two pools synced (store.Sync) ---- */
+/* bsg_pool_merge appends to dst the selected blobs of src whose refs dst does not hold, on the
+ * device: src's entries are probed in dst's index where both lie, no table crosses the host link.
+ * Selection. Without BSG_MERGE_ALL the selected blobs are the live ones of bsg_pool_collect's
+ * mark, rule for rule: it reads src's device table and index, fills status[] and info->gc the same
+ * way, returns the same BSG_ENOTFOUND / BSG_ECORRUPT and becomes the engine's current gc result.
+ * With BSG_MERGE_ALL every entry of src is selected, no mark runs, info->gc is all zero and the
+ * engine's gc result is left as it was.
+ * The append. Selected blob k of src is appended iff dst's index does not hold table[k].ref. Refs
+ * are trusted labels: a ref that dst holds with another len counts as known and is not replaced
+ * (store/mem's Put keeps the first blob, store/mem/mem.go:70-74). The appended blobs keep src's
+ * index order; the j-th becomes dst's entry first_blob + j = {off, len, ref} with off =
+ * align16(dst's bytes before the call) + the sum of align16(len) over the blobs appended before
+ * it, the padding is zero, and dst's `bytes` is the end of the last appended blob (unchanged when
+ * added == 0). dst afterwards equals, byte for byte over its allocation and entry for entry, a
+ * pool into which the same blobs were put one at a time in that order; it is a function of the two
+ * pools and the Roots alone, and serves puts, walk, restore, read, gc, collect and further merges
+ * like any other pool. A merge into an empty dst with Roots is a bsg_pool_collect whose table
+ * happens to be the same. A merge of an empty src succeeds with added == 0, and nroots == 0
+ * without BSG_MERGE_ALL selects nothing and succeeds.
+ * remap. dst owns a remap of src's nblobs entries at the call: remap[k] is the dst index that
+ * carries blob k's ref, appended now or known before, and UINT64_MAX for an unselected blob.
+ * bsg_pool_copy_remap and bsg_pool_remap_device serve it, as after a collect. dst's where[] is
+ * left untouched: the indices it holds stay valid.
+ * BSG_MERGE_VERIFY. After the probe and the plan, the blobs to append, and no others, are hashed
+ * on the engine's hash runs and held to their refs, as BSG_READ_VERIFY does for touched blobs. A
+ * mismatch returns BSG_ECORRUPT with bad_blob set, before anything of dst is written. Known and
+ * unselected blobs are never hashed, so `verified` is added_bytes on success.
+ * All or nothing. The mark, the probe, the plan, the verification and the readback of the totals
+ * write nothing of dst. After a failed mark, a failed verification or BSG_ENOMEM (need_blobs >
+ * cap_blobs, need_bytes > cap_bytes, or a workspace that cannot be allocated) dst is exactly as it
+ * was: bytes, table, index, counters, remap and where[]; info is filled as far as the call came.
+ * A device error after that point marks dst dead, as for a put. src is never written.
+ * Errors, in this order: BSG_EINVAL for a null engine or pool, src == dst, pools or engine on
+ * different devices, unknown flag bits, BSG_MERGE_ALL together with Roots or with
+ * BSG_GC_MISSING_LEAVES, nroots > 2^32 - 1 or null roots with a count; BSG_ESTATE if either pool
+ * is dead or the engine has an enqueued, unfinished run; the mark's codes; BSG_ECORRUPT from the
+ * verification; BSG_ENOMEM; BSG_EDEVICE. Synchronous, on the engine's stream. Both pools' mutexes
+ * are held for the whole call and taken together, as for bsg_pool_collect. The engine's last run,
+ * its dedup, tree, walk and restore results stay valid. */
+/* flags: BSG_GC_MISSING_LEAVES (1, the mark's, as for collect) */
+#define BSG_MERGE_ALL    2  /* select every blob of src; no mark; roots must be NULL, nroots 0 */
+#define BSG_MERGE_VERIFY 4  /* hash every blob that would be appended, and only those, first */
+typedef struct bsg_pool_merge_info {
+  bsg_gc_info gc;          /* what bsg_engine_gc_mark fills; all zero with BSG_MERGE_ALL */
+  uint64_t selected;       /* live blobs of src (all of them with BSG_MERGE_ALL) */
+  uint64_t added;          /* blobs appended to dst */
+  uint64_t added_bytes;    /* sum of their len */
+  uint64_t known;          /* selected blobs whose ref dst held before the call */
+  uint64_t first_blob;     /* dst's nblobs before the call */
+  uint64_t need_bytes, need_blobs; /* what dst would hold after; filled on capacity BSG_ENOMEM too */
+  uint64_t bad_blob;       /* VERIFY: smallest src index to append whose bytes do not hash to its ref, else UINT64_MAX */
+  uint64_t verified;       /* VERIFY: sum of len over the blobs hashed */
+} bsg_pool_merge_info;
+int bsg_pool_merge(bsg_engine* eng, bsg_pool* src, bsg_pool* dst,
+                   const uint8_t* roots, uint64_t nroots, int flags,
+                   int32_t* status /* host, nroots, or NULL */,
+                   bsg_pool_merge_info* info /* or NULL */);
+/* store.Sync (store/sync.go:14-126) for two pools: afterwards both hold the same set of refs. The
+ * pools end as after bsg_pool_merge(a -> b, BSG_MERGE_ALL) followed by bsg_pool_merge(b -> a,
+ * BSG_MERGE_ALL), but all or nothing across both directions: both probes, both plans, both
+ * verifications (with the flag) and both capacity checks run before either pool is written, each
+ * direction against the other pool as it stands at the call (what the first direction appends to
+ * b, a holds already). If either direction would not fit the call returns BSG_ENOMEM with both
+ * infos filled and both pools unchanged. info[0] is a -> b, info[1] b -> a, its `selected` b's
+ * nblobs at the call; b's remap covers a's blobs at the call and a's remap b's. The errors are
+ * merge's, with a == b in the place of src == dst and any flag but BSG_MERGE_VERIFY unknown. */
+int bsg_pool_sync(bsg_engine* eng, bsg_pool* a, bsg_pool* b, int flags /* 0 or BSG_MERGE_VERIFY */,
+                  bsg_pool_merge_info info[2] /* [0]: a -> b, [1]: b -> a; or NULL */);
+
 /* Empties a pool for reuse, so two pools can alternate as source and destination: the counters go
  * to zero, the index, the table and the used bytes are refilled as at creation, where[] and remap
  * are dropped (their device pointers return NULL). A dead pool is usable again. Afterwards the
