@@ -185,6 +185,19 @@ class PoolMergeInfo(ctypes.Structure):
 
 
 assert ctypes.sizeof(PoolMergeInfo) == 144
+GET_VERIFY = 1         # BSG_GET_VERIFY (Pool.get)
+
+
+class PoolGetInfo(ctypes.Structure):
+    """bsg_pool_get_info (include/bsgpu.h)."""
+    _fields_ = [(k, ctypes.c_uint64) for k in
+                ("found", "missing", "bytes", "need_bytes", "bad_blob", "verified")]
+
+    def as_dict(self) -> dict:
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+assert ctypes.sizeof(PoolGetInfo) == 48
 READ_VERIFY = 1        # BSG_READ_VERIFY (Engine.read, Pool.read)
 READ_RANGE_DTYPE = np.dtype([("root", "u1", (32,)), ("offset", "<u8"), ("len", "<u8")])
 assert READ_RANGE_DTYPE.itemsize == 48
@@ -347,6 +360,11 @@ def lib() -> ctypes.CDLL:
         "bsg_pool_sync": (ctypes.c_int, [vp, vp, vp, ctypes.c_int, ctypes.POINTER(PoolMergeInfo)]),
         "bsg_pool_merge_ms_debug": (ctypes.c_int, [vp, ctypes.c_int,
                                                    ctypes.POINTER(ctypes.c_float)]),
+        "bsg_pool_put_blobs": (ctypes.c_int, [vp, vp, vp, u64p, u64p, ctypes.c_uint64,
+                                              ctypes.c_int, vp, ctypes.POINTER(POOL_PUT_INFO)]),
+        "bsg_pool_get": (ctypes.c_int, [vp, vp, vp, ctypes.c_uint64, vp, ctypes.c_uint64,
+                                        ctypes.c_int, vp, vp, ctypes.POINTER(PoolGetInfo)]),
+        "bsg_pool_blobs_ms_debug": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_float)]),
         "bsg_engine_pack_mode_debug": (ctypes.c_int, [vp, ctypes.c_int]),
         "bsg_engine_d2d_ms_debug": (ctypes.c_int, [vp, vp, vp, ctypes.c_uint64,
                                                    ctypes.POINTER(ctypes.c_float)]),
@@ -1316,6 +1334,58 @@ class Pool:
                                  len(rg), op, out_cap, oo.ctypes.data, flags, status.ctypes.data,
                                  got.ctypes.data, ctypes.byref(info))
         return rc, status[:len(rg)], got[:len(rg)], info.as_dict()
+
+    def put_blobs(self, eng: "Engine", src, off, lens, flags: int = 0):
+        """bsg_pool_put_blobs: the blobs src[off[i] .. off[i] + lens[i]) (a DeviceBuffer or a
+        device address) hashed on `eng` and the new ones appended. Returns (rc, info, refs): the
+        return code, the bsg_pool_put_info as a dict and the blobs' refs ([n, 32] uint8); a
+        negative rc is returned, not raised. where() serves the items' blob indices."""
+        sp = src.ptr if isinstance(src, DeviceBuffer) else src
+        oo, ll = _u64(off), _u64(lens)
+        assert len(oo) == len(ll)
+        refs = np.zeros((max(len(oo), 1), 32), dtype=np.uint8)
+        info = POOL_PUT_INFO()
+        rc = lib().bsg_pool_put_blobs(eng.h if eng is not None else None, self.h, sp,
+                                      _p(oo, ctypes.c_uint64), _p(ll, ctypes.c_uint64), len(oo),
+                                      flags, refs.ctypes.data, ctypes.byref(info))
+        if rc == BSG_OK:
+            self._items = int(info.items)
+        return rc, info.as_dict(), refs[:len(oo)]
+
+    def get(self, eng: "Engine", refs, out=None, verify: bool = False,
+            out_cap: int | None = None, flags: int | None = None):
+        """bsg_pool_get: the blobs under `refs` ([n, 32] uint8, n * 32 bytes or a list of
+        32-byte refs) gathered into `out` (a DeviceBuffer, or a device address with out_cap;
+        None: nothing is gathered, a Has / size call). Returns (rc, info, idx, out_off): the
+        return code, the bsg_pool_get_info as a dict, every request's blob index (NONE64 for a
+        missing ref) and its place in `out` (n + 1 entries); a negative rc is returned, not
+        raised."""
+        if isinstance(refs, (list, tuple)):
+            refs = b"".join(bytes(r) for r in refs)
+        refs = np.ascontiguousarray(np.frombuffer(refs, dtype=np.uint8)
+                                    if isinstance(refs, (bytes, bytearray)) else refs,
+                                    dtype=np.uint8).reshape(-1)
+        assert len(refs) % 32 == 0
+        n = len(refs) // 32
+        op = out.ptr if isinstance(out, DeviceBuffer) else out
+        if out_cap is None:
+            out_cap = out.nbytes if isinstance(out, DeviceBuffer) else 0
+        idx = np.zeros(max(n, 1), dtype=np.uint64)
+        out_off = np.zeros(n + 1, dtype=np.uint64)
+        info = PoolGetInfo()
+        fl = (GET_VERIFY if verify else 0) if flags is None else flags
+        rc = lib().bsg_pool_get(eng.h if eng is not None else None, self.h,
+                                refs.ctypes.data if n else None, n, op, out_cap, fl,
+                                idx.ctypes.data, out_off.ctypes.data, ctypes.byref(info))
+        return rc, info.as_dict(), idx[:n], out_off
+
+    def blobs_ms(self, eng: "Engine") -> dict:
+        """The last put_blobs() and the last get() on `eng` in ms (test tooling; needs the
+        engine's profile() on)."""
+        out = (ctypes.c_float * 6)()
+        _check(lib().bsg_pool_blobs_ms_debug(eng.h, out), "bsg_pool_blobs_ms_debug")
+        return dict(zip(("hash", "plan", "append", "probe", "verify", "gather"),
+                        (float(x) for x in out)))
 
     def remap(self) -> np.ndarray:
         """bsg_pool_copy_remap: for every blob index of the source of the last successful collect

@@ -3,7 +3,8 @@
 // read-only lookup, the index of a pool's blobs), the search for the segment that holds a
 // position and the per-thread gather of 16-byte output vectors from segments. Included from
 // bsgpu_kernels.hip before bsgpu_tree.inc, bsgpu_dedup.inc, bsgpu_restore.inc, bsgpu_walk.inc,
-// bsgpu_gc.inc, bsgpu_pool.inc and bsgpu_read.inc, inside namespace bsg. DESIGN §4.6b.
+// bsgpu_gc.inc, bsgpu_pool.inc, bsgpu_read.inc and bsgpu_blobs.inc, inside namespace bsg.
+// DESIGN §4.6b.
 
 // workgroups of a grid-stride pass over `items`, 256 threads each
 static inline uint32_t engine_grid(uint64_t items, int num_cus) {

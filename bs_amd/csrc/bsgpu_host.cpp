@@ -1,8 +1,8 @@
 // bsgpu_host.cpp — libbsgpu host side: the C ABI declared in include/bsgpu.h. What it drives
 // lives in the headers included below, one per concern: host_mem.h (buffers, streams, knobs),
 // host_engine.h (the run pipeline; it includes the passes host_tree.h, host_dedup.h,
-// host_restore.h, host_walk.h, host_gc.h and host_blobpool.h), host_stream.h (copy pool, streaming
-// context), host_hasher.h.
+// host_restore.h, host_walk.h, host_gc.h, host_read.h, host_blobpool.h and host_blobs.h),
+// host_stream.h (copy pool, streaming context), host_hasher.h.
 //
 // A run = one launch sequence over a batch of stream segments (bsgpu_internal.h):
 //   k_start (descriptors in, counters zeroed) → k_scan (+ its exact pass) → prefix(strip counts) →
@@ -738,6 +738,71 @@ int bsg_pool_sync(bsg_engine* e, bsg_pool* a, bsg_pool* b, int flags, bsg_pool_m
 extern "C" int bsg_pool_merge_ms_debug(const bsg_engine* e, int dir, float out[5]) {
   if (!e || !out || dir < 0 || dir > 1) return BSG_EINVAL;
   for (int i = 0; i < 5; ++i) out[i] = e->merge[dir].ms[i];
+  return BSG_OK;
+}
+
+// ---- blobs put into a pool and got out of it by ref -------------------------------------------
+static_assert(sizeof(bsg_pool_get_info) == 48, "bsg_pool_get_info layout");
+
+int bsg_pool_put_blobs(bsg_engine* e, bsg_pool* p, const uint8_t* d_src, const uint64_t* off,
+                       const uint64_t* len, uint64_t nblobs, int flags, uint8_t* refs_out,
+                       bsg_pool_put_info* info) {
+  bsg_pool_put_info none{};
+  if (info) *info = none;
+  if (!e || !p || flags || nblobs >= (1ull << 32) || (nblobs && (!d_src || !off || !len)) ||
+      p->dev != e->dev || reinterpret_cast<uintptr_t>(d_src) % 16 != 0)
+    return BSG_EINVAL;
+  uint64_t hi = 0;  // an empty blob's offset counts too: it is still an address in d_src
+  for (uint64_t i = 0; i < nblobs; ++i) {
+    if (off[i] % 16 != 0 || len[i] >= (1ull << 40) || off[i] > UINT64_MAX - len[i])
+      return BSG_EINVAL;
+    hi = std::max<uint64_t>(hi, off[i] + len[i]);
+  }
+  int rc = e->setdev();
+  if (rc) return rc;
+  if (nblobs) {  // the read slack behind the last blob, as bsg_engine_hash
+    hipDeviceptr_t base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)d_src) != hipSuccess) {
+      (void)hipGetLastError();
+      return BSG_EINVAL;  // not a HIP device allocation
+    }
+    const uint64_t avail = (uint64_t)((const uint8_t*)base + size - d_src);
+    if (avail < kReadSlack || hi > avail - kReadSlack) return BSG_EINVAL;
+  }
+  std::lock_guard<std::mutex> g(p->mu);
+  // the source may not lie in the pool's own allocation: the append writes there
+  const uintptr_t s0 = reinterpret_cast<uintptr_t>(d_src), s1 = s0 + hi;
+  const uintptr_t p0 = reinterpret_cast<uintptr_t>(p->bytes.p), p1 = p0 + p->pool_bytes();
+  if (s0 < p1 && p0 < s1) return BSG_EINVAL;
+  if (p->dead || e->enqueued) return BSG_ESTATE;
+  return e->blobs.put(e->view(), *p, d_src, hi, off, len, nblobs, refs_out, info ? info : &none);
+}
+
+int bsg_pool_get(bsg_engine* e, bsg_pool* p, const uint8_t* refs, uint64_t nrefs, uint8_t* d_out,
+                 uint64_t out_cap, int flags, uint64_t* idx, uint64_t* out_off,
+                 bsg_pool_get_info* info) {
+  if (info) *info = bsg_pool_get_info{0, 0, 0, 0, UINT64_MAX, 0};
+  const uintptr_t o0 = reinterpret_cast<uintptr_t>(d_out), o1 = o0 + out_cap;
+  if (!e || !p || !info || (flags & ~BSG_GET_VERIFY) || nrefs >= (1ull << 32) || (!refs && nrefs) ||
+      o0 % 16 != 0 || (!d_out) != (!out_cap) || o1 < o0 || p->dev != e->dev)
+    return BSG_EINVAL;
+  std::lock_guard<std::mutex> g(p->mu);
+  const uintptr_t p0 = reinterpret_cast<uintptr_t>(p->bytes.p), p1 = p0 + p->pool_bytes();
+  if (d_out && o0 < p1 && p0 < o1) return BSG_EINVAL;  // the output inside the pool
+  if (p->dead || e->enqueued) return BSG_ESTATE;
+  int rc = e->setdev();
+  if (rc) return rc;
+  return e->blobs.get(e->view(), *p, refs, nrefs, d_out, out_cap, flags, idx, out_off, info);
+}
+
+// Test and measurement tooling (not in bsgpu.h): the last bsg_pool_put_blobs on e (the hash runs,
+// first occurrence + plan, append + gather) and its last bsg_pool_get (probe + sum, verify,
+// gather) in ms, timed with HIP events on the engine's stream when bsg_engine_profile is on (else
+// zeros).
+extern "C" int bsg_pool_blobs_ms_debug(const bsg_engine* e, float out[6]) {
+  if (!e || !out) return BSG_EINVAL;
+  for (int i = 0; i < 6; ++i) out[i] = e->blobs.ms[i];
   return BSG_OK;
 }
 

@@ -382,4 +382,22 @@ struct MergeHdr {
 };
 static_assert(sizeof(MergeHdr) % 16 == 0 && offsetof(MergeHdr, r) % 16 == 0, "MergeHdr layout");
 
+// Blobs put into a pool and got out of it by ref (bsg_pool_put_blobs, bsg_pool_get;
+// bsgpu_blobs.inc). A put's item i is src[span[i].off .. + span[i].len), its ref the hash runs'.
+struct BlobSpan {
+  uint64_t off;
+  uint64_t len;
+};
+struct GetHdr {                // one get's verdicts and totals, read back by the host
+  RestoreHdr r;                // r.dd.error: the bug guard of the probe, the verification and the
+                               //   gather; r.invalid bit 4; r.bad_blob: the smallest found blob
+                               //   that does not hash to its ref
+  uint64_t found;              // requests whose ref the pool holds
+  uint64_t bytes;              // their blobs' lens, summed
+  uint64_t verified;           // the hashed blobs' lens, summed
+  uint64_t pad_;
+  uint8_t zero[16];            // the bytes of the padding
+};
+static_assert(sizeof(GetHdr) % 16 == 0 && offsetof(GetHdr, zero) % 16 == 0, "GetHdr layout");
+
 }  // namespace bsg

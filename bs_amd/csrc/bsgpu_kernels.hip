@@ -2628,6 +2628,7 @@ hipError_t launch_sha_blobs(const BlobShaArgs& a, hipStream_t s, int num_cus) {
 #include "bsgpu_gc.inc"
 #include "bsgpu_pool.inc"
 #include "bsgpu_read.inc"
+#include "bsgpu_blobs.inc"
 #include "bsgpu_tail.inc"
 
 }  // namespace bsg

@@ -546,4 +546,49 @@ hipError_t launch_read_descs(const TouchArgs& a, uint64_t t0, uint32_t n, Stream
 hipError_t launch_read_compare(const TouchArgs& a, uint64_t t0, uint32_t n, const ChunkRec* hashed,
                                const Counters* hctr, hipStream_t s, int num_cus);
 
+// bsg_pool_put_blobs (bsgpu_blobs.inc): bsg_engine_pool_put with blobs of the caller's in the place
+// of records and nodes. p is the put's block with p.d over refs (stride 32) and the spans' lens
+// (stride 16); p.data .. p.arena_bytes are unused. span, src, src_bytes and refs belong to the call:
+// every span lies in [0, src_bytes), held to that by the host before the upload and by every kernel
+// that forms an address from one.
+struct BlobPutArgs {
+  PoolArgs p;
+  const BlobSpan* span;      // [p.d.n]
+  const uint8_t* src;
+  uint64_t src_bytes;        // the end of the last blob's last byte
+  uint8_t* refs;             // [p.d.n * 32] the hash runs' refs
+};
+// blobs [b0, b0 + n) as the descriptors of a hash run, and that run's refs into refs[]
+hipError_t launch_blob_descs(const BlobPutArgs& a, uint64_t b0, uint32_t n, StreamDesc* d,
+                             hipStream_t s, int num_cus);
+hipError_t launch_blob_refs(const BlobPutArgs& a, uint64_t b0, uint32_t n, const ChunkRec* hashed,
+                            const Counters* hctr, hipStream_t s, int num_cus);
+// launch_pool_gather for the blobs: new blob k's bytes are item p.d.uniq[k]'s span of src
+hipError_t launch_pool_gather_blobs(const BlobPutArgs& a, hipStream_t s);
+
+// bsg_pool_get (bsgpu_blobs.inc): n refs probed in a pool's index, the found blobs' bytes gathered
+// in request order, each rounded up to 16 with zero padding. pool .. index_mask are the pool as it
+// stands and are only read; refs .. hdr belong to the call. launch_get_probe writes idx, out_off,
+// touched and the header; total is out_off[n], read back and held to the output's capacity before
+// launch_get_gather writes out[0 .. total).
+struct GetArgs {
+  const uint8_t* pool;
+  uint64_t pool_bytes;
+  const PoolBlob* table;
+  uint64_t nblobs;
+  const uint64_t* index;     // [index_mask + 1] blob indices by ref
+  uint64_t index_mask;
+  const uint8_t* refs;       // [n * 32]
+  uint64_t n;
+  uint64_t* idx;             // [n] request q's blob, or kDedupEmpty
+  uint64_t* out_off;         // [n + 1] exclusive prefix of the found blobs' lens rounded up to 16
+  uint64_t* part;            // [sum_parts(n)] workgroup sums of the prefix pass
+  uint8_t* touched;          // [nblobs] set for every found blob (null: not wanted)
+  GetHdr* hdr;
+  uint64_t total;
+  uint8_t* out;
+};
+hipError_t launch_get_probe(const GetArgs& a, hipStream_t s, int num_cus);
+hipError_t launch_get_gather(const GetArgs& a, hipStream_t s);
+
 }  // namespace bsg

@@ -96,7 +96,10 @@ __device__ __forceinline__ const uint8_t* pool_src(const PoolArgs& a, uint64_t u
 
 // Partitioned by output tiles of kPoolTile bytes, as k_pack and k_gc_compact. Segment k is new
 // blob k: its bytes at base + seg16[k], then the zero bytes (at most 15) up to seg16[k + 1].
-__global__ __launch_bounds__(256) void k_pool_gather(PoolArgs a) {
+// src(u, len): where item u's len bytes lie (pool_src for a run's items; bsgpu_blobs.inc has the
+// one for a caller's blobs).
+template <class Src>
+__device__ __forceinline__ void pool_gather_tiles(const PoolArgs& a, Src src) {
   const uint64_t t0 = (uint64_t)blockIdx.x * kPoolTile;
   if (t0 >= a.total16 || !a.nnew) return;
   const uint64_t t1 = min(t0 + (uint64_t)kPoolTile, a.total16);
@@ -123,7 +126,7 @@ __global__ __launch_bounds__(256) void k_pool_gather(PoolArgs a) {
       return false;
     }
     if (pos - o < len) {
-      g->src = pool_src(a, u, len);
+      g->src = src(u, len);
       g->b0 = o;
       g->b1 = o + len;
     } else {
@@ -133,6 +136,10 @@ __global__ __launch_bounds__(256) void k_pool_gather(PoolArgs a) {
     }
     return g->src != nullptr;
   });
+}
+
+__global__ __launch_bounds__(256) void k_pool_gather(PoolArgs a) {
+  pool_gather_tiles(a, [&a](uint64_t u, uint64_t len) { return pool_src(a, u, len); });
 }
 
 // ---- where: every item's blob -----------------------------------------------------------------

@@ -1,7 +1,8 @@
 // host_blobpool.h — bsg_pool, bsg_engine_pool_put and bsg_pool_collect: a pool of blobs that lives
 // in device memory across runs, the last finished run's new chunks and tree nodes appended to it,
-// and a pool's live blobs collected into an empty pool (included by host_engine.h). Not
-// host_pool.h (the copy threads) and not DevicePool (idle engines).
+// and a pool's live blobs collected into an empty pool (included by host_engine.h). The put of a
+// caller's blobs (host_blobs.h) goes through the same put_items. Not host_pool.h (the copy
+// threads) and not DevicePool (idle engines).
 #pragma once
 
 // The pool owns its bytes, its blob table and its index of blob indices by ref, none of which
@@ -66,10 +67,43 @@ struct bsg_pool {
                       offsetof(ChunkRec, len) == offsetof(TreeNode, blob_len),
                   "records and nodes are one kind of item");
     const hipStream_t s = v.stream;
-    auto stamp = [&](size_t i) { v.profile ? marks.record(i, s) : void(); };
     const uint64_t nrec = (flags & BSG_POOL_CHUNKS) ? v.nrec : 0;
     const uint64_t nn = tree ? tree->plan.nn : 0;
-    const uint64_t n = nrec + nn;
+    return put_items(
+        v, nrec + nn, false, info,
+        [&](PoolArgs& a) {
+          const uint8_t* rec = reinterpret_cast<const uint8_t*>(v.rec);
+          a.d.refs = rec + offsetof(ChunkRec, ref);
+          a.d.lens = rec + offsetof(ChunkRec, len);
+          a.d.stride = a.d.len_stride = sizeof(ChunkRec);
+          a.d.n1 = nrec;
+          if (nn) {
+            const uint8_t* nd = tree->nodes.as<uint8_t>();
+            a.d.refs2 = nd + offsetof(TreeNode, ref);
+            a.d.lens2 = nd + offsetof(TreeNode, blob_len);
+            a.nodes = tree->nodes.as<TreeNode>();
+            a.arena = tree->arena.as<uint8_t>();
+            a.arena_bytes = tree->plan.arena;
+          }
+          a.data = v.d_data;
+          a.streams = v.streams;
+          a.nstreams = v.ns;
+          a.rec = v.rec;
+        },
+        [](const PoolArgs&) { return BSG_OK; },
+        [&](const PoolArgs& a) { return dbg("launch_pool_gather", s, launch_pool_gather(a, s)); });
+  }
+
+  // A put of n items, whatever they are. items(a) names them: a.d's refs and lens, and what the
+  // gather needs to find their bytes; refs(a) enqueues what makes the refs, if they do not stand
+  // yet (bsg_pool_put_blobs: the hash runs; its device checks flag a.d.hdr); gather(a) launches
+  // the new blobs' bytes. empty_ok: an item may have no bytes (a run's chunks and nodes all have
+  // some, so new items without bytes are a fault there).
+  template <class Items, class Refs, class Gather>
+  int put_items(const RunView& v, uint64_t n, bool empty_ok, bsg_pool_put_info* info, Items items,
+                Refs refs, Gather gather) {
+    const hipStream_t s = v.stream;
+    auto stamp = [&](size_t i) { v.profile ? marks.record(i, s) : void(); };
     bsg_pool_put_info out{};
     out.items = n;
     out.first_blob = out.need_blobs = nblobs;
@@ -85,19 +119,9 @@ struct bsg_pool {
     if ((rc = work.reserve(n))) return rc;
     MCHECK(off16.ensure(8 * (n + 1)));
     MCHECK(seg16.ensure(8 * (n + 1)));
-    const uint8_t* rec = reinterpret_cast<const uint8_t*>(v.rec);
     PoolArgs a{};
-    a.d = work.args(rec + offsetof(ChunkRec, ref), sizeof(ChunkRec), rec + offsetof(ChunkRec, len),
-                    sizeof(ChunkRec), n);
-    a.d.n1 = nrec;
-    if (nn) {
-      const uint8_t* nd = tree->nodes.as<uint8_t>();
-      a.d.refs2 = nd + offsetof(TreeNode, ref);
-      a.d.lens2 = nd + offsetof(TreeNode, blob_len);
-      a.nodes = tree->nodes.as<TreeNode>();
-      a.arena = tree->arena.as<uint8_t>();
-      a.arena_bytes = tree->plan.arena;
-    }
+    a.d = work.args(nullptr, 0, nullptr, 0, n);
+    items(a);
     a.d.set_keys = table.as<uint8_t>() + offsetof(PoolBlob, ref);
     a.d.set_stride = sizeof(PoolBlob);
     a.d.set_tab = index.as<uint64_t>();
@@ -105,10 +129,6 @@ struct bsg_pool {
     a.d.set_count = nblobs;
     a.hdr = hdr.as<PoolHdr>();
     a.d.hdr = &a.hdr->dd;
-    a.data = v.d_data;
-    a.streams = v.streams;
-    a.nstreams = v.ns;
-    a.rec = v.rec;
     a.off16 = off16.as<uint64_t>();
     a.seg16 = seg16.as<uint64_t>();
     a.bytes = bytes.as<uint8_t>();
@@ -119,8 +139,9 @@ struct bsg_pool {
     a.base = pad16(used);
 
     // first occurrence and offsets: the call's own buffers and the header, nothing of the pool
-    stamp(0);
     HCHECK(hipMemsetAsync(hdr.p, 0, sizeof(PoolHdr), s));
+    if ((rc = refs(a))) return rc;
+    stamp(0);
     HCHECK(work.tab.clear(s));
     HCHECK(dbg("launch_dedup", s, launch_dedup(a.d, s, v.num_cus)));
     HCHECK(dbg("launch_pool_plan", s, launch_pool_plan(a, s, v.num_cus)));
@@ -128,7 +149,8 @@ struct bsg_pool {
     PoolHdr h;
     if ((rc = readback(s, &h))) return rc;
     if (h.dd.nunique > n || h.total16 % 16 || pad16(h.last_len) > h.total16 ||
-        (h.dd.nunique == 0) != (h.total16 == 0) || h.dd.unique_bytes > h.total16)
+        (h.dd.nunique == 0 && h.total16) || (!empty_ok && h.dd.nunique && !h.total16) ||
+        h.dd.unique_bytes > h.total16)
       return BSG_EDEVICE;
     out.added = h.dd.nunique;
     out.added_bytes = h.dd.unique_bytes;
@@ -149,7 +171,7 @@ struct bsg_pool {
     stamp(2);
     hipError_t e = dbg("launch_pool_append", s, launch_pool_append(a, s, v.num_cus));
     stamp(3);
-    if (e == hipSuccess) e = dbg("launch_pool_gather", s, launch_pool_gather(a, s));
+    if (e == hipSuccess) e = gather(a);
     stamp(4);
     if (e == hipSuccess) e = dbg("launch_pool_where", s, launch_pool_where(a, s, v.num_cus));
     stamp(5);

@@ -90,6 +90,7 @@ int hash_batches(bsg_engine* owner, DevBuf& dbuf, uint64_t n, const uint8_t* dat
 #include "host_gc.h"
 #include "host_read.h"
 #include "host_blobpool.h"
+#include "host_blobs.h"
 
 struct bsg_engine {
   int dev = 0;
@@ -185,6 +186,7 @@ struct bsg_engine {
   GcWork gc;
   ReadWork read;
   MergeWork merge[2];  // bsg_pool_merge uses the first, bsg_pool_sync one per direction
+  BlobWork blobs;
   RunView view() {
     return RunView{this, stream, num_cus, profile, run_done, run_done && !snapshot && !hash_mode,
                    enqueued, d_data, &descs, streams.as<StreamDesc>(), nstreams,

@@ -686,6 +686,84 @@ int bsg_pool_merge(bsg_engine* eng, bsg_pool* src, bsg_pool* dst,
 int bsg_pool_sync(bsg_engine* eng, bsg_pool* a, bsg_pool* b, int flags /* 0 or BSG_MERGE_VERIFY */,
                   bsg_pool_merge_info info[2] /* [0]: a -> b, [1]: b -> a; or NULL */);
 
+/* ---- blobs put into a pool and got out of it by ref: bs.PutMulti / bs.GetMulti ---- */
+/* bsg_pool_put_blobs is store/mem's Put (bs.PutMulti, multi.go:84-143, its batched form) for blobs
+ * that are not part of a split run: fs.Dir and schema blobs, anchors, whatever a server receives.
+ * Layout. Item i is d_src[off[i] .. off[i] + len[i]) under bsg_engine_hash's rules: d_src and every
+ * off[i] multiples of 16, len[i] < 2^40, off[i] + len[i] without wrap, BSG_READ_SLACK readable
+ * bytes after the last blob in d_src's allocation; any order, gaps, overlapping or coinciding
+ * blobs and empty blobs are fine. nblobs is not capped at 65,535 (the call hashes in batches); it
+ * is refused from 2^32 on.
+ * Refs. Every item's SHA-256 is computed on the device, on the engine's hash runs; a ref is never
+ * taken from the caller (Put computes blob.Ref()). refs_out, when given, receives them, item
+ * order, also when the call ends in BSG_ENOMEM for want of capacity.
+ * The append. From the refs on the call is bsg_engine_pool_put with these items in the place of
+ * records and nodes: item i is appended iff the pool does not hold its ref and no item j < i
+ * carries it; the k-th appended item gets entry first_blob + k at align16(bytes before the call) +
+ * the sum of align16(len) over the items appended before it; padding is zero; an empty blob takes
+ * an entry and no bytes. bsg_pool_put_info is filled as for a put. A pool fed a run's chunks and
+ * then its nodes this way, in the order of bsg_engine_chunks_device and
+ * bsg_engine_tree_nodes_device, is byte for byte and entry for entry the pool bsg_engine_pool_put
+ * makes, and serves walk, restore, read, gc, collect and merge alike.
+ * where[]. bsg_pool_copy_where / bsg_pool_where_device hold item i's blob index afterwards. Item
+ * i's ref was added by this call iff where[i] >= first_blob (PutMulti's map[Ref]bool); the item
+ * that brought the bytes is the first with that where.
+ * All or nothing, as a put: BSG_ENOMEM (need_bytes > cap_bytes, need_blobs > cap_blobs, or no
+ * workspace) leaves the pool and where[] untouched, with info filled in the first two cases; a
+ * device error during the append marks the pool dead.
+ * Errors, in this order: BSG_EINVAL for a null engine or pool, flags != 0, a null pointer with a
+ * count, nblobs >= 2^32, a pool on another device, a layout rule broken, or a source that
+ * intersects the pool's allocation; BSG_ESTATE for a dead pool or an engine with an enqueued,
+ * unfinished run; BSG_ENOMEM; BSG_EDEVICE. nblobs == 0 succeeds and leaves where NULL.
+ * Synchronous, on the engine's stream; the pool's mutex is held for the whole call. The engine's
+ * last run and its dedup, tree, walk, restore and gc results stay valid. info may be NULL. */
+int bsg_pool_put_blobs(bsg_engine* eng, bsg_pool* pool,
+                       const uint8_t* d_src,                     /* device */
+                       const uint64_t* off, const uint64_t* len, /* host, nblobs */
+                       uint64_t nblobs, int flags /* 0 */,
+                       uint8_t* refs_out /* host, nblobs x 32, or NULL */,
+                       bsg_pool_put_info* info /* or NULL */);
+
+/* bsg_pool_get is store/mem's Get (bs.GetMulti, multi.go:10-69, its batched form): request q, the
+ * ref refs[32q .. 32q + 32), is probed in the pool's own device index; nothing of the table
+ * crosses the host link.
+ * Placement. idx[q] is the blob's index or UINT64_MAX. out_off[q] is the exclusive prefix sum, in
+ * request order, of align16(len) for found requests and 0 for missing ones; out_off[nrefs] is the
+ * total. A ref asked for twice gets two copies.
+ * The result is partial, as GetMulti's: a missing ref is no error of the call, which returns
+ * BSG_OK with idx[q] == UINT64_MAX and info->missing counted.
+ * Output. d_out[out_off[q] .. + len) holds the blob and the padding up to the next multiple of 16
+ * is written zero; no byte at or past out_off[nrefs] is written. The output is therefore itself a
+ * valid source for bsg_pool_put_blobs and bsg_engine_hash (given the read slack behind it).
+ * With d_out == NULL and out_cap == 0 nothing is gathered (a Has / size call); idx, out_off and
+ * info are filled all the same.
+ * BSG_GET_VERIFY. The distinct found blobs, and no others, are hashed on the engine's hash runs
+ * and held to their refs before a byte of d_out is written, as BSG_READ_VERIFY does for touched
+ * blobs. A mismatch returns BSG_ECORRUPT with bad_blob set and nothing written.
+ * Errors, in this order: BSG_EINVAL for a null engine, pool or info, null refs with a count,
+ * unknown flag bits, nrefs >= 2^32, d_out not a multiple of 16, d_out NULL with out_cap != 0 or
+ * the reverse, a pool on another device, or an output range that intersects the pool's
+ * allocation; BSG_ESTATE for a dead pool or an engine with an enqueued, unfinished run;
+ * BSG_ENOMEM if need_bytes > out_cap, with info, idx and out_off filled and d_out untouched, or
+ * for want of workspace; BSG_ECORRUPT; BSG_EDEVICE. The pool is never written and never marked
+ * dead by a get. Synchronous, on the engine's stream; the pool's mutex is held for the whole
+ * call. The engine's last run and its dedup, tree, walk, restore and gc results stay valid. */
+#define BSG_GET_VERIFY 1
+typedef struct bsg_pool_get_info {
+  uint64_t found, missing;   /* over the request, repeats counted each time */
+  uint64_t bytes;            /* sum of len over found requests */
+  uint64_t need_bytes;       /* out_off[nrefs]; filled on BSG_ENOMEM too */
+  uint64_t bad_blob;         /* VERIFY: smallest pool index that fails, else UINT64_MAX */
+  uint64_t verified;         /* VERIFY: sum of len over the distinct blobs hashed */
+} bsg_pool_get_info;
+int bsg_pool_get(bsg_engine* eng, bsg_pool* pool,
+                 const uint8_t* refs, uint64_t nrefs,   /* host, nrefs x 32 */
+                 uint8_t* d_out, uint64_t out_cap,      /* device, or NULL with 0 */
+                 int flags,
+                 uint64_t* idx,      /* host, nrefs: blob index or UINT64_MAX; or NULL */
+                 uint64_t* out_off,  /* host, nrefs + 1; or NULL */
+                 bsg_pool_get_info* info);
+
 /* Empties a pool for reuse, so two pools can alternate as source and destination: the counters go
  * to zero, the index, the table and the used bytes are refilled as at creation, where[] and remap
  * are dropped (their device pointers return NULL). A dead pool is usable again. Afterwards the
