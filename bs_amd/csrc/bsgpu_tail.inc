@@ -69,7 +69,7 @@ __global__ void k_offload_cut(TailArgs a) {
   TailHdr* h = a.hdr;
   const bool dead = a.ctr->overflow || a.ctr->error || a.ctr->nchunks > a.chunk_cap;
   const uint64_t mx = a.ctr->max_nblocks;
-  uint64_t n = 0, B = 0, K = 0;
+  uint64_t n = 0, B = 0, K = 0, low = kTailBuckets;  // low: the lowest bucket taken so far
   uint64_t best_cut = kTailBuckets, best_n = 0, best_B = 0, best_K = 0, best_left = mx;
   float best_cost = (float)mx * a.us_per_block;
   const uint32_t floor = tail_floor(a);
@@ -84,12 +84,12 @@ __global__ void k_offload_cut(TailArgs a) {
       const float cost = fmaxf(gpu, host);
       if (a.force_cut || cost < best_cost) {
         best_cost = cost;
-        best_cut = (uint64_t)(b + 1), best_n = n, best_B = B, best_K = K, best_left = left;
+        best_cut = low, best_n = n, best_B = B, best_K = K, best_left = left;
       }
     }
     if (b < 0) break;
     if (n + h->cnt[b] > a.max_items || B + h->rbytes[b] > a.ring_bytes) break;
-    n += h->cnt[b], B += h->rbytes[b], K += h->nblk[b];
+    n += h->cnt[b], B += h->rbytes[b], K += h->nblk[b], low = (uint64_t)b;
   }
   uint32_t at = 0;
   for (int b = (int)kTailBuckets - 1; b >= (int)best_cut; --b) {

@@ -13,28 +13,21 @@ would also take early chains: the tail takes their chunks, no early pick is made
 written once; (f) the portable hash; (g) two runs without a finish between them; (h) the knob
 off; (i) a ring that holds only the longest candidate; (j) a hash run behind an unfinished run with
 a tail; (k) the cost model's own cut on a 512 MiB stream, the engine's own threshold."""
-import contextlib
-
 import pytest
 
 import early_cases as C
+import tail_cases as T
 
 pytestmark = pytest.mark.gpu
 L, _c = C.L, C._c
-SHORT = [1100, 1300, 1197, 1250, 1111, 1400]     # 18 to 22 blocks
-
-
-def _plan(longs, tail=("r", 700)):
-    plan = _c(SHORT[0], SHORT[1])
-    for i, n in enumerate(longs):
-        plan += _c(n, SHORT[(i + 2) % len(SHORT)])
-    return plan + [tail]
+SHORT, _plan = T.SHORT, T.plan
+_tuples, _device, _run, _result, _split, _check, _blocks = (T.tuples, T.device, T.run, T.result,
+                                                            T.split, T.check, T.blocks)
 
 
 def _cases():
-    three = [L(2050, 55), L(1705, 56), L(1333, 1)]
     return {
-        "three": C.Case("tail-three", [_plan(three)], 101),
+        "three": T.three(),
         "edges": C.Case("tail-edges", [_plan([L(1200, 55), L(1300, 56), L(1400, 0), L(1500, 1)])],
                         102),
         "streams": C.Case("tail-streams", [_plan([]), _plan([L(1600, 7), L(1250, 56)]), _plan([]),
@@ -53,58 +46,6 @@ def cases(table, oracle):
             c.build(table)
             _BUILT[k] = (c, C.expect(c, oracle, table))
     return _BUILT
-
-
-def _tuples(ch):
-    return [(int(c["offset"]), int(c["len"]), int(c["level"]), bytes(c["ref"]).hex(),
-             int(c["stream"])) for c in ch]
-
-
-@contextlib.contextmanager
-def _device(gpu, case):
-    host = case.buffer()
-    buf = gpu.DeviceBuffer(host.size)
-    try:
-        buf.from_host(host)
-        yield buf
-    finally:
-        buf.free()
-
-
-def _run(eng, buf, case):
-    eng.run(buf.ptr, case.off, case.lens, bits=case.bits, min_size=case.min_size)
-
-
-def _result(eng):
-    return {"records": _tuples(eng.chunks()), "counts": [int(x) for x in eng.counts()],
-            "tail": eng.diag()["host_tail"], "early": eng.tiers()["early"]}
-
-
-def _split(gpu, case, early=False, **tail):
-    with _device(gpu, case) as buf:
-        eng = gpu.Engine()
-        try:
-            eng.set_host_tail(0, **tail)
-            if early:
-                eng.set_early_min(0)
-            _run(eng, buf, case)
-            eng.finish()
-            return _result(eng)
-        finally:
-            eng.close()
-
-
-def _check(got, want, what):
-    bad = next((i for i, (g, w) in enumerate(zip(got["records"], want["records"])) if g != w),
-               min(len(got["records"]), len(want["records"])))
-    assert got["records"] == want["records"], (what, "first difference at record", bad,
-                                               want["records"][bad:bad + 1],
-                                               got["records"][bad:bad + 1])
-    assert got["counts"] == want["counts"], what
-
-
-def _blocks(n):
-    return (n + 8) // 64 + 1
 
 
 @pytest.mark.parametrize("cut,chunks", [(5000, 0), (2000, 1), (1000, 3), (1, None)])
